@@ -18,8 +18,18 @@ Other BASELINE.json configs as extra workloads (not the default line):
                        2-in/2-out transfers (1 : 4) at 32-bit range, 1 % tampered,
                        one fts_actions_verify_batch per step, actions/s
 
+A plain run sets up, warms up, times the K steps and prints the result line.
+--full adds, after the timed steps, everything that takes runs of its own: the
+CPU baselines, the host-inclusive rate, the isolated calls behind the
+per-kernel and roofline figures (those fields are null without it).
+--dump-outputs DIR writes what the last timed step returned to its callers as
+DIR/<name>.npy (for the default workload also the exact transcript scalars and
+com of a fixed sample of proofs, from one pass of the timed region's size run
+after the clock); the inputs are seeded, so two builds can be compared output
+for output.
+
 Prints one JSON line (rank 0).  Usage:
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--bits 64]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--bits 64] [--full] [--dump-outputs DIR]
   python bench.py --workload msm --msm-log 20
   torchrun --nproc-per-node N bench.py --gpus N ...
 """
@@ -162,6 +172,47 @@ def _action_cpu_baseline(pp_raw, bits, actions, want, args, unit, what):
     return cpu
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def _dump_outputs(args, rank, arrays):
+    """--dump-outputs DIR: the arrays the last timed step returned, as DIR/<name>.npy
+    (rank 0).  Integer verdicts and bytes are stored as float32 (exact below 2^24), each
+    byte of a field element or point as one value;
+    an output that would take the dump past 64 MB is cut to a fixed, seeded sample."""
+    if not args.dump_outputs or rank != 0:
+        return
+    import numpy as np
+    os.makedirs(args.dump_outputs, exist_ok=True)
+    budget = DUMP_MAX_BYTES // max(1, len(arrays))
+    for name, a in arrays.items():
+        if isinstance(a, (bytes, bytearray)):
+            a = np.frombuffer(bytes(a), dtype=np.uint8)
+        a = np.asarray(a)
+        a = np.ascontiguousarray(a, dtype=np.float64 if a.dtype == np.float64 else np.float32)
+        if a.nbytes > budget:
+            keep = np.sort(np.random.default_rng(0xF7A5D0).choice(a.size, budget // a.itemsize, replace=False))
+            a = a.reshape(-1)[keep]
+        np.save(os.path.join(args.dump_outputs, name + ".npy"), a)
+
+
+def _rp_intermediates(pp, idx):
+    """exact values the last range-proof pass computed for its proofs `idx`, read back
+    from the device (fts_debug_rp_intermediates): the 8 + 2k transcript scalars
+    [x, x^2, y, y^-1, z, z^2, polEval, x0, x_j.., x_j^-1..] (32-byte BE Fr each) and the
+    point com (64-byte BE) -> two uint8 arrays, one row per proof"""
+    import numpy as np
+    from fts_gpu import _lib as FL
+    ch = ctypes.create_string_buffer(32 * (8 + 2 * pp.rounds))
+    com = ctypes.create_string_buffer(64)
+    rows = ([], [])
+    for i in idx:
+        FL.check("fts_debug_rp_intermediates", FL.lib.fts_debug_rp_intermediates(pp._ctx, int(i), ch, com, None))
+        for r, buf in zip(rows, (ch, com)):
+            r.append(np.frombuffer(buf.raw, dtype=np.uint8))
+    return tuple(np.stack(r) for r in rows)
+
+
 def _cg_throttle():
     """(nr_throttled, throttled_usec) of this process's cgroup (v2), if readable"""
     try:
@@ -226,7 +277,17 @@ def main():
                     help="concurrent verify calls (host threads) of the non-C2 workloads; default 8 for the "
                          "action workloads (transfer / mixed / request: the library coalesces concurrent calls "
                          "into shared passes, as a validator's goroutines would submit them), 3 otherwise")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need, after the timed steps: CPU baselines, "
+                         "the host-inclusive rate, isolated calls for the per-kernel / roofline figures "
+                         "(--cpu-sample, --cpu-seconds, --host-steps and --roofline-steps apply only here)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned to its caller as "
+                         "DIR/<name>.npy (float32 / float64)")
     args = ap.parse_args()
+    if not args.full:
+        args.cpu_sample = 0
+        args.host_steps = 0
     if args.action_inflight is None:
         args.action_inflight = (8 if args.workload in ("transfer", "mixed", "request")
                                 else 8 if args.workload == "identity" else 3)
@@ -385,76 +446,118 @@ def main():
 
     total = world * B * args.steps
     value = total / elapsed
+    if args.dump_outputs:
+        # res lists every slot's steps in slot order: the verdicts each in-flight slot's
+        # caller received from its last timed step, one row of B per slot
+        per = [args.steps // inflight + (1 if i < args.steps % inflight else 0) for i in range(inflight)]
+        ends = np.cumsum(per)
+        dump = {"status": np.stack([res[e - 1][0] for e, c in zip(ends, per) if c > 0])}
+        # Honest proofs give all-zero verdicts, so the dump also holds what the pass computes on
+        # the way to them.  The last timed pass holds whichever batches met in it, in arrival
+        # order, so after the clock one pass of the timed region's size (the first FTS_COALESCE_MAX /
+        # batch staged batches as one batch, the work path) runs alone, and the exact transcript
+        # scalars and com of a fixed sample of its proofs are read back from the device.
+        if rank == 0:
+            mb = args.pass_batches or max(1, int(os.environ.get("FTS_COALESCE_MAX", "81920")) // B)
+            sel = [staged[i % len(staged)] for i in range(mb)]
+            one = pp.stage_range_proofs([p for ps, _ in sel for p in ps], [c for _, cs in sel for c in cs])
+            st = one.verify(want_status=True)
+            assert (st == np.concatenate([wants[i % len(wants)] for i in range(mb)])).all()
+            pick = np.sort(np.random.default_rng(0xF7A5D1).choice(mb * B, min(256, mb * B), replace=False))
+            dump["pass_sample_index"] = pick
+            dump["pass_sample_status"] = st[pick]
+            dump["pass_sample_scalars"], dump["pass_sample_com"] = _rp_intermediates(pp, pick)
+            one.close()
+        _dump_outputs(args, rank, dump)
 
-    # Isolated passes (after the timed region), so each kernel's HIP-event
-    # time is its own (in the pipelined region kernels of several passes share
-    # the CUs and their event spans overlap):
-    #  1. one 4,096-proof batch alone: the single-batch latency view;
-    #  2. one pass of the size the timed region ran (merged_batches_avg
-    #     batches, coalesced), alone: the ROOFLINE launch -- run last, so the
-    #     last R dispatches of a rocprofv3 trace / PMC pass are exactly these.
-    R = max(1, args.roofline_steps)
+    # --full only: everything below the timed region that takes runs of its own
+    # (isolated passes for the per-kernel roofline, the host-inclusive rate, the
+    # CPU baselines); a plain run reports the headline figure alone
+    if args.full:
+        # Isolated passes (after the timed region), so each kernel's HIP-event
+        # time is its own (in the pipelined region kernels of several passes share
+        # the CUs and their event spans overlap):
+        #  1. one 4,096-proof batch alone: the single-batch latency view;
+        #  2. one pass of the size the timed region ran (merged_batches_avg
+        #     batches, coalesced), alone: the ROOFLINE launch -- run last, so the
+        #     last R dispatches of a rocprofv3 trace / PMC pass are exactly these.
+        R = max(1, args.roofline_steps)
 
-    def isolated(batch, reps, want):
-        acc = {}
-        t = time.perf_counter()
-        for _ in range(reps):
-            st = batch.verify(want_status=True)
-            assert (st == want).all()
-            for name, (ms, mads) in batch.timings().items():
-                o = acc.get(name, (0.0, 0.0))
-                acc[name] = (o[0] + ms, mads)
-        return acc, (time.perf_counter() - t) * 1e3 / reps
+        def isolated(batch, reps, want):
+            acc = {}
+            t = time.perf_counter()
+            for _ in range(reps):
+                st = batch.verify(want_status=True)
+                assert (st == want).all()
+                for name, (ms, mads) in batch.timings().items():
+                    o = acc.get(name, (0.0, 0.0))
+                    acc[name] = (o[0] + ms, mads)
+            return acc, (time.perf_counter() - t) * 1e3 / reps
 
-    kt1, iso_ms = isolated(batches[0], R, wants[0])
-    m = args.pass_batches or max(1, int(os.environ.get("FTS_COALESCE_MAX", "81920")) // B)
-    pass_proofs = [staged[i % len(staged)] for i in range(m)]
-    big = pp.stage_range_proofs([p for ps, _ in pass_proofs for p in ps], [c for _, cs in pass_proofs for c in cs])
-    kt, pass_ms = isolated(big, R, np.concatenate([wants[i % len(wants)] for i in range(m)]))
-    big.close()
-    avg = {kname: v[0] / R for kname, v in kt.items()}
-    avg1 = {kname: v[0] / R for kname, v in kt1.items()}
-    # roofline kernel: the largest share of the algorithmic work (MADs/launch);
-    # the longest (latency-bound) kernel is reported beside it
-    dom = max(kt, key=lambda kname: kt[kname][1])
-    dom1 = max(kt1, key=lambda kname: kt1[kname][1])  # a lone batch may take the latency path's kernels
-    longest = max((kn for kn in avg if not kn.startswith("host_")), key=avg.get)
+        kt1, iso_ms = isolated(batches[0], R, wants[0])
+        m = args.pass_batches or max(1, int(os.environ.get("FTS_COALESCE_MAX", "81920")) // B)
+        pass_proofs = [staged[i % len(staged)] for i in range(m)]
+        big = pp.stage_range_proofs([p for ps, _ in pass_proofs for p in ps], [c for _, cs in pass_proofs for c in cs])
+        kt, pass_ms = isolated(big, R, np.concatenate([wants[i % len(wants)] for i in range(m)]))
+        big.close()
+        avg = {kname: v[0] / R for kname, v in kt.items()}
+        avg1 = {kname: v[0] / R for kname, v in kt1.items()}
+        # roofline kernel: the largest share of the algorithmic work (MADs/launch);
+        # the longest (latency-bound) kernel is reported beside it
+        dom = max(kt, key=lambda kname: kt[kname][1])
+        dom1 = max(kt1, key=lambda kname: kt1[kname][1])  # a lone batch may take the latency path's kernels
+        longest = max((kn for kn in avg if not kn.startswith("host_")), key=avg.get)
 
-    def kernel_roof(kname):
-        ms, mads = avg[kname], kt[kname][1]
-        ach = mads / (ms * 1e-3) / 1e12 if mads and ms > 0 else None
-        return {"kernel": kname, "kernel_ms": round(ms, 4), "mads_per_launch": mads,
-                "achieved": round(ach, 3) if ach else None, "frac": round(ach / PEAK_TMAD, 4) if ach else None}
+        def kernel_roof(kname):
+            ms, mads = avg[kname], kt[kname][1]
+            ach = mads / (ms * 1e-3) / 1e12 if mads and ms > 0 else None
+            return {"kernel": kname, "kernel_ms": round(ms, 4), "mads_per_launch": mads,
+                    "achieved": round(ach, 3) if ach else None, "frac": round(ach / PEAK_TMAD, 4) if ach else None}
 
-    # this pipeline's own cost model: algorithmic MADs of every kernel of one pass / proofs
-    own_mads = sum(v[1] for v in kt.values()) / (m * B)
-    traffic = None
-    tj_path = args.traffic_json
-    if tj_path is None:
-        import glob
-        cands = sorted(glob.glob(os.path.join(ROOT, "profiles", "traffic_r[0-9][0-9].json")))
-        tj_path = cands[-1] if cands else ""
-    try:
-        with open(tj_path) as f:
-            tj = json.load(f)
-            # HBM bytes per launch of THIS pass size: FETCH_SIZE (scaled by the factor calibrated for the
-            # kernel's access pattern, tools/fetch_calib) + WRITE_SIZE, from separate PMC runs of the same command
-            e = tj.get("%s@pass%d" % (dom, m * B), {})
-            if e.get("fetch_bytes") is not None:
-                traffic = int(e["fetch_bytes"] * e.get("fetch_scale", 1.0) + e.get("write_bytes", 0))
-    except (OSError, ValueError, AttributeError):
-        pass
-    rd = kernel_roof(dom)
-    roofline = {"bound": "int32_valu (v_mad_u64_u32)", "kernel": dom, "achieved": rd["achieved"],
-                "peak": round(PEAK_TMAD, 3), "unit": "TMAD/s", "frac": rd["frac"], "traffic": traffic,
-                "traffic_source": os.path.basename(tj_path) if traffic is not None else None,
-                "kernel_ms": rd["kernel_ms"], "mads_per_launch": rd["mads_per_launch"],
-                "measured": "HIP events, %d isolated passes of %d proofs (%d coalesced batches, the timed region's "
-                            "pass size) alone on the GPU after the timed region" % (R, m * B, m),
-                "pipeline_frac_survey_model": round(value / world * SURVEY_MAD_PER_RP64 / (PEAK_TMAD * 1e12), 4),
-                "pipeline_mads_per_rp64": round(own_mads),
-                "pipeline_frac_own_model": round(value / world * own_mads / (PEAK_TMAD * 1e12), 4)}
-    longest_kernel = kernel_roof(longest)
+        # this pipeline's own cost model: algorithmic MADs of every kernel of one pass / proofs
+        own_mads = sum(v[1] for v in kt.values()) / (m * B)
+        traffic = None
+        tj_path = args.traffic_json
+        if tj_path is None:
+            import glob
+            cands = sorted(glob.glob(os.path.join(ROOT, "profiles", "traffic_r[0-9][0-9].json")))
+            tj_path = cands[-1] if cands else ""
+        try:
+            with open(tj_path) as f:
+                tj = json.load(f)
+                # HBM bytes per launch of THIS pass size: FETCH_SIZE (scaled by the factor calibrated for the
+                # kernel's access pattern, tools/fetch_calib) + WRITE_SIZE, from separate PMC runs of the same command
+                e = tj.get("%s@pass%d" % (dom, m * B), {})
+                if e.get("fetch_bytes") is not None:
+                    traffic = int(e["fetch_bytes"] * e.get("fetch_scale", 1.0) + e.get("write_bytes", 0))
+        except (OSError, ValueError, AttributeError):
+            pass
+        rd = kernel_roof(dom)
+        roofline = {"bound": "int32_valu (v_mad_u64_u32)", "kernel": dom, "achieved": rd["achieved"],
+                    "peak": round(PEAK_TMAD, 3), "unit": "TMAD/s", "frac": rd["frac"], "traffic": traffic,
+                    "traffic_source": os.path.basename(tj_path) if traffic is not None else None,
+                    "kernel_ms": rd["kernel_ms"], "mads_per_launch": rd["mads_per_launch"],
+                    "measured": "HIP events, %d isolated passes of %d proofs (%d coalesced batches, the timed region's "
+                                "pass size) alone on the GPU after the timed region" % (R, m * B, m),
+                    "pipeline_frac_survey_model": round(value / world * SURVEY_MAD_PER_RP64 / (PEAK_TMAD * 1e12), 4),
+                    "pipeline_mads_per_rp64": round(own_mads),
+                    "pipeline_frac_own_model": round(value / world * own_mads / (PEAK_TMAD * 1e12), 4)}
+        longest_kernel = kernel_roof(longest)
+        iso = {"isolated_batch": {"ms": round(iso_ms, 3), "verifies_per_s": round(B / iso_ms * 1e3, 1),
+                                  "note": "one %d-proof batch alone on the GPU (latency; no coalescing)" % B,
+                                  "roofline_kernel": dom1,
+                                  "roofline_kernel_ms": round(avg1.get(dom1, 0.0), 4),
+                                  "roofline_frac": round(kt1[dom1][1] / (avg1[dom1] * 1e-3) / 1e12 / PEAK_TMAD, 4)
+                                  if avg1.get(dom1) else None},
+               "isolated_pass": {"proofs": m * B, "ms": round(pass_ms, 3),
+                                 "verifies_per_s": round(m * B / pass_ms * 1e3, 1)},
+               "roofline": roofline,
+               "longest_kernel": longest_kernel,
+               "kernel_ms_isolated": {kname: round(v, 4) for kname, v in avg.items()},
+               "fallback": _fallback_share(kt, R, pass_ms)}
+    else:
+        iso = dict.fromkeys(("isolated_batch", "isolated_pass", "roofline", "longest_kernel", "kernel_ms_isolated",
+                             "fallback"))
 
     # the drop-in boundary from host buffers, after the timed region: DER bytes in
     # (fts_rp_verify_batch: host parse + upload + verify + verdicts back), the
@@ -529,21 +632,16 @@ def main():
             "device_lanes": args.lanes,
             "merged_batches_avg": round(merged_avg, 2),
             "host": host,
-            "isolated_batch": {"ms": round(iso_ms, 3), "verifies_per_s": round(B / iso_ms * 1e3, 1),
-                               "note": "one %d-proof batch alone on the GPU (latency; no coalescing)" % B,
-                               "roofline_kernel": dom1,
-                               "roofline_kernel_ms": round(avg1.get(dom1, 0.0), 4),
-                               "roofline_frac": round(kt1[dom1][1] / (avg1[dom1] * 1e-3) / 1e12 / PEAK_TMAD, 4)
-                               if avg1.get(dom1) else None},
-            "isolated_pass": {"proofs": m * B, "ms": round(pass_ms, 3), "verifies_per_s": round(m * B / pass_ms * 1e3, 1)},
+            "isolated_batch": iso["isolated_batch"],
+            "isolated_pass": iso["isolated_pass"],
             "host_inclusive": host_inclusive,
-            "roofline": roofline,
-            "longest_kernel": longest_kernel,
+            "roofline": iso["roofline"],
+            "longest_kernel": iso["longest_kernel"],
             "cpu_baseline": cpu,
-            "kernel_ms_isolated": {kname: round(v, 4) for kname, v in avg.items()},
+            "kernel_ms_isolated": iso["kernel_ms_isolated"],
             "tampered": args.tamper,
             "tamper_every": args.tamper_every,
-            "fallback": _fallback_share(kt, R, pass_ms),
+            "fallback": iso["fallback"],
             "prove_s": round(prove_s, 2),
             "library": _lib_record(),
             # fixed-base tables resident in HBM: 16-bit windows for the 2n + 6 public
@@ -687,6 +785,11 @@ def _run_action_steps(batches, steps, dist, gather):
     return elapsed, outs
 
 
+def _last_outputs(outs):
+    """what every in-flight caller of _run_action_steps received from its last call, in caller order"""
+    return [o[-1] for o in outs if o]
+
+
 def bench_msm(args):
     world, rank, local, dist = _dist_setup()
     import random
@@ -731,11 +834,12 @@ def bench_msm(args):
     t0 = time.perf_counter()
     kt = {}
     for _ in range(args.steps):
-        st.run()
+        res = st.run()
         for name, (ms, mads) in st.timings().items():
             o = kt.get(name, (0.0, 0.0))
             kt[name] = (o[0] + ms, mads)
     elapsed = _max_over_ranks(dist, time.perf_counter() - t0)
+    _dump_outputs(args, rank, {"msm_result": res})
     value = world * n * args.steps / elapsed
     cpu = None
     if rank == 0 and world == 1 and args.cpu_sample > 0:
@@ -826,12 +930,15 @@ def bench_prove(args):
             self.s += 1
             return pp.prove_range_batch_gpu(vals, bfs, seed=1 + (self.i * 1000 + self.s) * n)
 
-    elapsed, _ = _run_action_steps([Step(i) for i in range(max(1, args.action_inflight))], args.steps, None, None)
+    elapsed, outs = _run_action_steps([Step(i) for i in range(max(1, args.action_inflight))], args.steps, None, None)
     elapsed = _max_over_ranks(dist, elapsed)
     value = world * n * args.steps / elapsed
-    kt = {}  # one call alone on the GPU (per-kernel view)
+    last = _last_outputs(outs)
+    _dump_outputs(args, rank, {"proofs": b"".join(p for o in last for p in o[0]),
+                               "commitments": b"".join(c for o in last for c in o[1])})
+    kt = {}  # one call alone on the GPU (per-kernel view; --full)
     reps = 2
-    for s in range(reps):
+    for s in range(reps if args.full else 0):
         pp.prove_range_batch_gpu(vals, bfs, seed=1)
         for name, (ms, mads) in pp.last_timings_ex().items():
             o = kt.get(name, (0.0, 0.0))
@@ -861,7 +968,8 @@ def bench_prove(args):
             "config": {"workload": "SURVEY 8f rank 2: %d range proofs per GPU per step via fts_rp_prove_batch_gpu, "
                                    "%d calls in flight" % (n, max(1, args.action_inflight)), "batch_per_gpu": n, "bit_length": args.bits,
                        "parallelism": "shard%d" % world},
-            "roofline": _roofline_from(kt, reps), "cpu_baseline": cpu, "inflight": max(1, args.action_inflight),
+            "roofline": _roofline_from(kt, reps) if kt else None, "cpu_baseline": cpu,
+            "inflight": max(1, args.action_inflight),
             "kernel_ms": {k: round(v[0] / reps, 4) for k, v in kt.items()}}), flush=True)
     if dist is not None:
         dist.destroy_process_group()
@@ -898,9 +1006,10 @@ def _bench_prove_transfers(args, pp, world, rank, dist):
             return pp.prove_transfers_gpu(wb, seed=1 + (self.i * 1000 + self.s) * n)
 
     wb = fts_gpu.WitnessBatch(trs, pp.rounds)  # packed once (host structs, reused by every call)
-    elapsed, _ = _run_action_steps([Step(i) for i in range(max(1, args.action_inflight))], args.steps, None, None)
+    elapsed, outs = _run_action_steps([Step(i) for i in range(max(1, args.action_inflight))], args.steps, None, None)
     elapsed = _max_over_ranks(dist, elapsed)
     value = world * n * args.steps / elapsed
+    _dump_outputs(args, rank, {"transfer_proofs": b"".join(p for o in _last_outputs(outs) for p in o)})
     cpu = None
     if rank == 0 and world == 1 and args.cpu_sample > 0:
         thr = max(1, min(args.cpu_threads, os.cpu_count() or 1))
@@ -987,13 +1096,14 @@ def bench_audit(args):
         steps_objs[0].verify()
     if dist is not None:
         dist.barrier()
-    elapsed, _ = _run_action_steps(steps_objs, args.steps, None, None)
+    elapsed, outs = _run_action_steps(steps_objs, args.steps, None, None)
     elapsed = _max_over_ranks(dist, elapsed)
     value = world * n * args.steps / elapsed
-    # isolated kernel time (one call alone on the GPU)
+    _dump_outputs(args, rank, {"status": np.stack(_last_outputs(outs))})
+    # isolated kernel time (one call alone on the GPU; --full)
     kt = {}
     reps = 4
-    for _ in range(reps):
+    for _ in range(reps if args.full else 0):
         steps_objs[0].verify()
         for name, (ms, mads) in pp.last_timings_ex().items():
             o = kt.get(name, (0.0, 0.0))
@@ -1025,7 +1135,7 @@ def bench_audit(args):
             "config": {"workload": "SURVEY 8f rank 3: %d token openings per GPU per step via fts_token_open_batch, "
                                    "%d calls in flight" % (n, len(batches)), "tokens_per_gpu": n,
                        "parallelism": "shard%d" % world},
-            "roofline": _roofline_from(kt, reps), "cpu_baseline": cpu,
+            "roofline": _roofline_from(kt, reps) if kt else None, "cpu_baseline": cpu,
             "kernel_ms": {k: round(v[0] / reps, 4) for k, v in kt.items()}, "setup_s": round(setup_s, 2)}),
             flush=True)
     if dist is not None:
@@ -1103,13 +1213,14 @@ def bench_ecdsa(args):
     # --action-inflight concurrent calls: each runs on its own library slot
     # (stream + staging), so one call's host parse/pack overlaps another's kernels
     inflight = max(1, args.action_inflight)
-    elapsed, _ = _run_action_steps([Step() for _ in range(inflight)], args.steps, None, None)
+    elapsed, outs = _run_action_steps([Step() for _ in range(inflight)], args.steps, None, None)
     elapsed = _max_over_ranks(dist, elapsed)
     value = world * n * args.steps / elapsed
-    # isolated kernel times (one call alone on the GPU), HIP events
+    _dump_outputs(args, rank, {"status": np.stack(_last_outputs(outs))})
+    # isolated kernel times (one call alone on the GPU), HIP events; --full
     reps = 4
     kt = {"k_ecdsa_digest": 0.0, "k_ecdsa_verify": 0.0}
-    for _ in range(reps):
+    for _ in range(reps if args.full else 0):
         step()
         for k, v in E.last_timings(local).items():
             kt[k] += v
@@ -1117,8 +1228,8 @@ def bench_ecdsa(args):
     muls = _ecdsa_muls_per_verify()
     mads = (n - len(bad)) * muls * MAD_PER_MUL + len(bad) * muls * MAD_PER_MUL  # tampered items run the full path
     ms = kt["k_ecdsa_verify"] / reps
-    ach = mads / (ms * 1e-3) / 1e12
-    roof = {"bound": "int32_valu (v_mad_u64_u32)", "kernel": "k_ecdsa_verify", "achieved": round(ach, 3),
+    ach = mads / (ms * 1e-3) / 1e12 if ms > 0 else 0.0
+    roof = None if not args.full else {"bound": "int32_valu (v_mad_u64_u32)", "kernel": "k_ecdsa_verify", "achieved": round(ach, 3),
             "peak": round(PEAK_TMAD, 3), "unit": "TMAD/s", "frac": round(ach / PEAK_TMAD, 4), "traffic": None,
             "kernel_ms": round(ms, 4), "mads_per_launch": mads, "muls_per_verify": muls,
             "measured": "HIP events around each launch on the library's stream, %d isolated calls after the "
@@ -1148,7 +1259,8 @@ def bench_ecdsa(args):
                                    "fts_ecdsa_verify_batch, %d calls in flight" % (n, inflight), "sigs_per_gpu": n, "msg_len": L,
                        "parallelism": "shard%d" % world},
             "roofline": roof, "cpu_baseline": cpu,
-            "kernel_ms": {k: round(v / reps, 4) for k, v in kt.items()}, "setup_s": round(setup_s, 2)}),
+            "kernel_ms": {k: round(v / reps, 4) for k, v in kt.items()} if args.full else {},
+            "setup_s": round(setup_s, 2)}),
             flush=True)
     if dist is not None:
         dist.destroy_process_group()
@@ -1226,11 +1338,12 @@ def bench_idemix(args):
     if dist is not None:
         dist.barrier()
     inflight = max(1, args.action_inflight)
-    elapsed, _ = _run_action_steps([Step() for _ in range(inflight)], args.steps, None, None)
+    elapsed, outs = _run_action_steps([Step() for _ in range(inflight)], args.steps, None, None)
     elapsed = _max_over_ranks(dist, elapsed)
     value = world * n * args.steps / elapsed
-    reps, kms = 4, 0.0
-    for _ in range(reps):
+    _dump_outputs(args, rank, {"status": np.stack(_last_outputs(outs))})
+    reps, kms = 4, 0.0  # isolated calls for the kernel's own time (--full)
+    for _ in range(reps if args.full else 0):
         step()
         kms += K.last_kernel_ms()
     ms = kms / reps
@@ -1238,8 +1351,9 @@ def bench_idemix(args):
     # <= 2 x 33 full additions (~64), beta and the on-curve check (5)
     muls = NYM_MULS_PER_VERIFY if bn else 2 * 16 * 11 + 14 * 11 + 128 * 7 + 64 * 16 + 5
     mads = n * muls * MAD_PER_MUL  # tampered items run the full path
-    ach = mads / (ms * 1e-3) / 1e12
-    roof = {"bound": "int32_valu (v_mad_u64_u32)", "kernel": "k_nym_verify" + ("" if bn else "_fbn"), "achieved": round(ach, 3),
+    ach = mads / (ms * 1e-3) / 1e12 if ms > 0 else 0.0
+    roof = None if not args.full else {
+            "bound": "int32_valu (v_mad_u64_u32)", "kernel": "k_nym_verify" + ("" if bn else "_fbn"), "achieved": round(ach, 3),
             "peak": round(PEAK_TMAD, 3), "unit": "TMAD/s", "frac": round(ach / PEAK_TMAD, 4), "traffic": None,
             "kernel_ms": round(ms, 4), "mads_per_launch": mads, "muls_per_verify": muls,
             "measured": "HIP events around each launch on the library's stream, %d isolated calls after the "
@@ -1274,7 +1388,8 @@ def bench_idemix(args):
             "config": {"workload": "SURVEY 8f rank 4 (idemix): %d owner signatures per GPU per step via "
                                    "fts_nym_verify_batch, %d calls in flight" % (n, inflight), "sigs_per_gpu": n,
                        "msg_len": L, "parallelism": "shard%d" % world},
-            "roofline": roof, "cpu_baseline": cpu, "kernel_ms": {"k_nym_verify" + ("" if bn else "_fbn"): round(ms, 4)},
+            "roofline": roof, "cpu_baseline": cpu,
+            "kernel_ms": {"k_nym_verify" + ("" if bn else "_fbn"): round(ms, 4)} if args.full else {},
             "setup_s": round(setup_s, 2)}), flush=True)
     if dist is not None:
         dist.destroy_process_group()
@@ -1335,11 +1450,12 @@ def bench_identity(args):
     if dist is not None:
         dist.barrier()
     inflight = max(1, args.action_inflight)
-    elapsed, _ = _run_action_steps([Step() for _ in range(inflight)], args.steps, None, None)
+    elapsed, outs = _run_action_steps([Step() for _ in range(inflight)], args.steps, None, None)
     elapsed = _max_over_ranks(dist, elapsed)
     value = world * n * args.steps / elapsed
-    reps, kt, kp = 4, 0.0, 0.0
-    for _ in range(reps):
+    _dump_outputs(args, rank, {"status": np.stack(_last_outputs(outs))})
+    reps, kt, kp = 4, 0.0, 0.0  # isolated calls for the two phases' own times (--full)
+    for _ in range(reps if args.full else 0):
         step()
         a, b = V.last_kernel_ms()
         kt, kp = kt + a, kp + b
@@ -1349,7 +1465,7 @@ def bench_identity(args):
     # kernels (k_idv_var's six GLV and eleven fixed-base products per identity); the
     # pairing phase is mostly the latency of the per-group pairings (a few waves)
     mads = n * ID_TVAL_MULS * MAD_PER_MUL
-    ach = mads / (kt * 1e-3) / 1e12
+    ach = mads / (kt * 1e-3) / 1e12 if kt > 0 else 0.0
     # HBM bytes of the three t-value launches at 65,536 identities (BN254), from the newest
     # profiles/identity_traffic_rNN.json (separate FETCH_SIZE / WRITE_SIZE rocprofv3 passes)
     traffic, tsrc = None, None
@@ -1363,13 +1479,14 @@ def bench_identity(args):
             tsrc = os.path.basename(cands[-1])
         except (IndexError, OSError, KeyError, ValueError):
             traffic = None
-    roof = {"bound": "int32_valu (v_mad_u64_u32)", "kernel": "k_idv_decode + k_idv_var + k_idv_tvals",
+    roof = None if not args.full else {
+            "bound": "int32_valu (v_mad_u64_u32)", "kernel": "k_idv_decode + k_idv_var + k_idv_tvals",
             "achieved": round(ach, 3), "peak": round(PEAK_TMAD, 3), "unit": "TMAD/s", "frac": round(ach / PEAK_TMAD, 4),
             "traffic": traffic, "traffic_source": tsrc, "kernel_ms": round(kt, 4), "mads_per_launch": mads,
             "muls_per_identity": ID_TVAL_MULS,
             "measured": "HIP events around the three launches on the library's stream, %d isolated calls after the "
                         "timed region (the Fp inversions are not counted as work)" % reps}
-    pairing = {"phase_ms": round(kp, 4), "groups": groups, "paired_one_by_one": paired,
+    pairing = {"phase_ms": round(kp, 4) if args.full else None, "groups": groups, "paired_one_by_one": paired,
                "batch_muls_per_identity": ID_BATCH_MULS,
                "note": "k_idv_bp_terms (two 64-bit GLV chains per identity), one randomised pairing product per "
                        "group of 256 (k_idv_bp_pair), one-by-one pairings only for failing groups; "
@@ -1406,7 +1523,8 @@ def bench_identity(args):
                                    "fts_idemix_identity_verify_batch, %d calls in flight" % (n, inflight),
                        "identities_per_gpu": n, "parallelism": "shard%d" % world},
             "roofline": roof, "cpu_baseline": cpu,
-            "kernel_ms": {"k_idv_tvals": round(kt, 4), "k_idv_pairing": round(kp, 4)}, "pairing_check": pairing,
+            "kernel_ms": {"k_idv_tvals": round(kt, 4), "k_idv_pairing": round(kp, 4)} if args.full else {},
+            "pairing_check": pairing,
             "tval_mads_per_identity": ID_TVAL_MULS * MAD_PER_MUL, "setup_s": round(setup_s, 2)}), flush=True)
     if dist is not None:
         dist.destroy_process_group()
@@ -1460,8 +1578,11 @@ def bench_transfer(args, raw_requests=False):
         dist.barrier()
     from fts_gpu import dist as fdist
     # host buffers in (the C-ABI parses the DER proofs), verdicts out
-    elapsed, _ = _run_action_steps(batches, args.steps, dist, lambda r: fdist.allgather_verdicts(dist, r[0]))
+    elapsed, outs = _run_action_steps(batches, args.steps, dist, lambda r: fdist.allgather_verdicts(dist, r[0]))
     elapsed = _max_over_ranks(dist, elapsed)
+    last = _last_outputs(outs)
+    names = ("status", "fail_action", "fail_index") if raw_requests else ("status", "fail_index")
+    _dump_outputs(args, rank, {name: np.stack([r[j] for r in last]) for j, name in enumerate(names)})
     kt = {k: (v[0] * args.steps, v[1]) for k, v in pp.last_timings_ex().items()}
     value = world * args.transfers * args.steps / elapsed
     cpu = None
@@ -1558,12 +1679,15 @@ def bench_mixed(args):
             assert set(np.nonzero(r[0])[0]) == bad_tr and set(np.nonzero(r[2])[0]) == bad_is
     kt = {k: (v[0] * args.steps, v[1]) for k, v in pp.last_timings_ex().items()}
     value = world * (n_tr + n_is) * args.steps / elapsed
+    last = _last_outputs(outs)
+    _dump_outputs(args, rank, {name: np.stack([r[j] for r in last]) for j, name in enumerate(
+        ("transfer_status", "transfer_fail_index", "issue_status", "issue_fail_index"))})
     # one call alone after the timed region: the fallback's own cost (in the
     # pipelined region the latency-bound fallback kernels share the CUs with the
-    # other calls' passes, which stretches their spans)
+    # other calls' passes, which stretches their spans); --full
     iso_reps = 3
     kti, t_iso = {}, time.perf_counter()
-    for _ in range(iso_reps):
+    for _ in range(iso_reps if args.full else 0):
         batches[0].verify()
         for kname, (ms, mads) in pp.last_timings_ex().items():
             o = kti.get(kname, (0.0, 0.0))
@@ -1598,9 +1722,9 @@ def bench_mixed(args):
                                    "per step (%d range proofs), %d calls in flight" % (2 * n_tr + 16 * n_is, nb),
                        "transfers_per_gpu": n_tr, "issues_per_gpu": n_is, "parallelism": "shard%d" % world},
             "roofline": _roofline_from(kt, args.steps), "cpu_baseline": cpu,
-            "fallback": _fallback_share(kti, iso_reps, iso_ms),
+            "fallback": _fallback_share(kti, iso_reps, iso_ms) if args.full else None,
             "fallback_pipelined": _fallback_share(kt, args.steps, elapsed / args.steps * nb * 1e3),
-            "isolated_call_ms": round(iso_ms, 3),
+            "isolated_call_ms": round(iso_ms, 3) if args.full else None,
             "kernel_ms_isolated": {k: round(v[0] / iso_reps, 4) for k, v in kti.items()},
             "kernel_ms": {k: round(v[0] / args.steps, 4) for k, v in kt.items()}, "setup_s": round(setup_s, 2)}),
             flush=True)

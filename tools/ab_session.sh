@@ -45,12 +45,12 @@ for s in "$@"; do case $s in
         done ;;
   s512) for L in $LIBS; do
           arm $L true; n=$ARM
-          arm $L step s512_$n 400 python3 -u bench.py --steps 512 --warmup 64 --cpu-sample 0 --host-steps 0
+          arm $L step s512_$n 400 python3 -u bench.py --full --steps 512 --warmup 64 --cpu-sample 0 --host-steps 0
           grep '^{' $OUT/s512_$n.log | tail -1 | python3 -c "import json,sys; d=json.load(sys.stdin); print('$n', d['value'], d['ms_per_step'], d['isolated_pass'], d['merged_batches_avg'])"
         done ;;
   s20) for L in $LIBS; do
           arm $L true; n=$ARM
-          arm $L step s20_$n 300 python3 -u bench.py --steps 20 --warmup 5 --cpu-sample 0 --host-steps 0
+          arm $L step s20_$n 300 python3 -u bench.py --full --steps 20 --warmup 5 --cpu-sample 0 --host-steps 0
           grep '^{' $OUT/s20_$n.log | tail -1 | python3 -c "import json,sys; d=json.load(sys.stdin); print('$n', d['value'], d['ms_per_step'], d['isolated_pass'], d['merged_batches_avg'])"
         done ;;
   onebad) for L in $LIBS; do

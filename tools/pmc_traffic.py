@@ -3,8 +3,8 @@ rocprofv3 PMC passes over the same bench command (tools/gpu_round_r02.sh).
 
 Inputs: the FETCH_SIZE and WRITE_SIZE counter CSVs of the bench command, the
 FETCH_SIZE CSV of lib/fetch_calib with the byte counts it printed, the bench
-JSON line of the PMC command (for the isolated pass size), and R = its
---roofline-steps.  The LAST R dispatches of every kernel are bench.py's isolated
+JSON line of the PMC command (bench.py --full, for the isolated pass size), and
+R = its --roofline-steps.  The LAST R dispatches of every kernel are bench.py's isolated
 roofline pass; their average is stored under "<kernel>@pass<proofs>".
 
 FETCH_SIZE counts memory-side read requests (KiB).  Its ratio to the bytes a

@@ -15,7 +15,7 @@ while IFS='|' read -r tag envs cmd; do
   tag=$(echo $tag); [ -z "$tag" ] && continue; case "$tag" in \#*) continue;; esac
   set -- $cmd
   case "$1" in
-    bench) shift; set -- python3 -u bench.py --cpu-sample 0 "$@";;
+    bench) shift; set -- python3 -u bench.py --full --cpu-sample 0 "$@";;
     burst) shift; set -- python3 -u tools/burst.py "$@";;
     pass)  shift; set -- python3 -u tools/pass_times.py "$@";;
   esac
