@@ -25,7 +25,6 @@
 
 #include <algorithm>
 #include <atomic>
-#include <condition_variable>
 #include <functional>
 #include <mutex>
 #include <thread>
@@ -34,8 +33,14 @@
 #include "../../include/fts_gpu.h"
 #include "common/sha256.hpp"
 #include "device/p256.hpp"
+#include "host/hip_owned.hpp"
 
 using namespace p256;
+using fts::DevBuf;
+using fts::Event;
+using fts::PinBuf;
+using fts::SlotRing;
+using fts::Stream;
 
 namespace fts {
 void host_parallel_for(size_t n, const std::function<void(size_t)>& f);  // fts_api.cpp (persistent host pool)
@@ -241,44 +246,27 @@ int cmp32(const uint8_t* a, const uint8_t* b) { return memcmp(a, b, 32); }
 // pinned host staging, so one call's host parse/pack overlaps another's kernels.
 constexpr int NSLOT = 3;
 struct Slot {
-  hipStream_t stream = nullptr;
+  Stream stream;
   uint32_t* d_table = nullptr;  // the device's shared table
-  uint8_t* d_msg = nullptr;
-  size_t msg_cap = 0;
-  uint8_t* d_rec = nullptr;  // rec | e | moff | mlen | status
-  size_t rec_cap = 0;
-  uint8_t* h_stage = nullptr;  // pinned host staging
-  size_t h_cap = 0;
-  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+  DevBuf d_msg;
+  DevBuf d_rec;     // rec | e | moff | mlen | status
+  PinBuf h_stage;   // pinned host staging
+  Event ev[3];
   float ms[2] = {0.f, 0.f};
 };
 struct DevState {
-  std::mutex mu;
-  std::condition_variable cv;
+  SlotRing<Slot, NSLOT> ring;  // its lock also guards init, init_err and ms
   bool init = false;
   int init_err = 0;  // a failed initialisation is cached (no re-allocation on every retry)
-  uint32_t* d_table = nullptr;
-  Slot slot[NSLOT];
-  bool busy[NSLOT] = {false, false, false};
+  DevBuf d_table;
   float ms[2] = {0.f, 0.f};  // k_ecdsa_digest, k_ecdsa_verify of the last finished call
 };
-DevState g_dev[16];
-
-struct SlotGuard {
-  DevState& G;
-  int k;
-  ~SlotGuard() {
-    // an error path may leave a copy or kernel queued on the slot's stream that
-    // still reads its pinned staging / device buffers: drain it before the next
-    // caller may reuse (or re-allocate) them
-    if (G.slot[k].stream) (void)hipStreamSynchronize(G.slot[k].stream);
-    std::lock_guard<std::mutex> l(G.mu);
-    G.ms[0] = G.slot[k].ms[0];
-    G.ms[1] = G.slot[k].ms[1];
-    G.busy[k] = false;
-    G.cv.notify_one();
-  }
-};
+// never destroyed: its owners would release streams and memory during static
+// destruction, when the HIP runtime may already be gone
+DevState& dev_state(int device) {
+  static DevState* g = new DevState[16];
+  return g[device];
+}
 
 #define ECHK(x)                                 \
   do {                                          \
@@ -349,51 +337,35 @@ int fts_ecdsa_verify_batch(int device, size_t n, const fts_ecdsa_item* items, in
   if (n == 0) return FTS_API_OK;
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || device >= ndev) return FTS_API_EDEVICE;
-  DevState& G = g_dev[device];
-  int k = -1;
+  DevState& G = dev_state(device);
   {
-    std::unique_lock<std::mutex> l(G.mu);
+    std::lock_guard<std::mutex> l(G.ring.mu);
     ECHK(hipSetDevice(device));
     if (G.init_err) return G.init_err;
     if (!G.init) {
       // all or nothing: on any failure release what was created and cache the error
-      hipStream_t s0 = nullptr;
-      bool ok = hipStreamCreateWithFlags(&s0, hipStreamNonBlocking) == hipSuccess &&
-                hipMalloc(&G.d_table, (size_t)FB_NW * FB_ND * 16 * 4) == hipSuccess;
+      Stream s0;
+      bool ok = s0.create() == hipSuccess && G.d_table.reserve((size_t)FB_NW * FB_ND * 16 * 4);
       if (ok) {
-        k_ecdsa_table<<<FB_NW * FB_ND / 256, 256, 0, s0>>>(G.d_table);
+        k_ecdsa_table<<<FB_NW * FB_ND / 256, 256, 0, s0>>>(G.d_table.as<uint32_t>());
         ok = hipGetLastError() == hipSuccess && hipStreamSynchronize(s0) == hipSuccess;
       }
-      if (s0) (void)hipStreamDestroy(s0);
-      for (auto& S : G.slot) {
-        ok = ok && hipStreamCreateWithFlags(&S.stream, hipStreamNonBlocking) == hipSuccess;
-        for (auto& e : S.ev) ok = ok && hipEventCreate(&e) == hipSuccess;
-        S.d_table = G.d_table;
+      for (auto& S : G.ring.slot) {
+        ok = ok && S.stream.create() == hipSuccess;
+        for (auto& e : S.ev) ok = ok && e.create() == hipSuccess;
+        S.d_table = G.d_table.as<uint32_t>();
       }
       if (!ok) {
-        for (auto& S : G.slot) {
-          for (auto& e : S.ev)
-            if (e) (void)hipEventDestroy(e), e = nullptr;
-          if (S.stream) (void)hipStreamDestroy(S.stream), S.stream = nullptr;
-          S.d_table = nullptr;
-        }
-        if (G.d_table) (void)hipFree(G.d_table), G.d_table = nullptr;
+        for (auto& S : G.ring.slot) S = Slot();
+        G.d_table.release();
         G.init_err = FTS_API_EDEVICE;
         return G.init_err;
       }
       G.init = true;
     }
-    G.cv.wait(l, [&] {
-      for (int j = 0; j < NSLOT; j++)
-        if (!G.busy[j]) return true;
-      return false;
-    });
-    for (int j = 0; j < NSLOT && k < 0; j++)
-      if (!G.busy[j]) k = j;
-    G.busy[k] = true;
   }
-  SlotGuard guard{G, k};
-  Slot& D = G.slot[k];
+  auto guard = G.ring.acquire([&G](Slot& S) { G.ms[0] = S.ms[0], G.ms[1] = S.ms[1]; });
+  Slot& D = guard.slot();
   ECHK(hipSetDevice(device));
   // host: parse + low-S + range checks, pack records and messages into one
   // pinned staging buffer (records | e | moff | mlen | status | messages),
@@ -406,14 +378,8 @@ int fts_ecdsa_verify_batch(int device, size_t n, const fts_ecdsa_item* items, in
     mtot += items[i].msg_len;
   }
   const size_t need = tot + mtot;
-  if (D.h_cap < need) {
-    if (D.h_stage) hipHostFree(D.h_stage);
-    D.h_stage = nullptr, D.h_cap = 0;
-    const size_t cap = need + need / 2;
-    if (hipHostMalloc(&D.h_stage, cap, hipHostMallocDefault) != hipSuccess) return D.h_stage = nullptr, FTS_API_ENOMEM;
-    D.h_cap = cap;
-  }
-  uint8_t* h = D.h_stage;
+  if (D.h_stage.cap < need && !D.h_stage.reserve(need + need / 2)) return FTS_API_ENOMEM;
+  uint8_t* h = D.h_stage.as<uint8_t>();
   uint32_t* hrec = reinterpret_cast<uint32_t*>(h);
   uint64_t* hoff = reinterpret_cast<uint64_t*>(h + rec_b + e_b);
   uint32_t* hlen = reinterpret_cast<uint32_t*>(h + rec_b + e_b + off_b);
@@ -448,30 +414,19 @@ int fts_ecdsa_verify_batch(int device, size_t n, const fts_ecdsa_item* items, in
   };
   const size_t CH = 2048, nch = (n + CH - 1) / CH;
   fts::host_parallel_for(nch, [&](size_t c) { pack(c * CH, std::min(n, (c + 1) * CH)); });
-  if (D.rec_cap < tot) {
-    if (D.d_rec) hipFree(D.d_rec);
-    D.d_rec = nullptr, D.rec_cap = 0;
-    const size_t cap = tot + tot / 2;
-    if (hipMalloc(&D.d_rec, cap) != hipSuccess) return D.d_rec = nullptr, FTS_API_ENOMEM;
-    D.rec_cap = cap;
-  }
-  if (D.msg_cap < std::max<size_t>(mtot, 1)) {
-    if (D.d_msg) hipFree(D.d_msg);
-    D.d_msg = nullptr, D.msg_cap = 0;
-    const size_t cap = mtot + mtot / 2 + 1;
-    if (hipMalloc(&D.d_msg, cap) != hipSuccess) return D.d_msg = nullptr, FTS_API_ENOMEM;
-    D.msg_cap = cap;
-  }
-  uint32_t* drec = reinterpret_cast<uint32_t*>(D.d_rec);
-  uint32_t* de = reinterpret_cast<uint32_t*>(D.d_rec + rec_b);
-  uint64_t* doff = reinterpret_cast<uint64_t*>(D.d_rec + rec_b + e_b);
-  uint32_t* dlen = reinterpret_cast<uint32_t*>(D.d_rec + rec_b + e_b + off_b);
-  int32_t* dst = reinterpret_cast<int32_t*>(D.d_rec + rec_b + e_b + off_b + len_b);
-  ECHK(hipMemcpyAsync(D.d_rec, h, tot, hipMemcpyHostToDevice, D.stream));
-  if (mtot) ECHK(hipMemcpyAsync(D.d_msg, hm, mtot, hipMemcpyHostToDevice, D.stream));
+  if (D.d_rec.cap < tot && !D.d_rec.reserve(tot + tot / 2)) return FTS_API_ENOMEM;
+  if (D.d_msg.cap < std::max<size_t>(mtot, 1) && !D.d_msg.reserve(mtot + mtot / 2 + 1)) return FTS_API_ENOMEM;
+  uint8_t* const d_rec = D.d_rec.as<uint8_t>();
+  uint32_t* drec = reinterpret_cast<uint32_t*>(d_rec);
+  uint32_t* de = reinterpret_cast<uint32_t*>(d_rec + rec_b);
+  uint64_t* doff = reinterpret_cast<uint64_t*>(d_rec + rec_b + e_b);
+  uint32_t* dlen = reinterpret_cast<uint32_t*>(d_rec + rec_b + e_b + off_b);
+  int32_t* dst = reinterpret_cast<int32_t*>(d_rec + rec_b + e_b + off_b + len_b);
+  ECHK(hipMemcpyAsync(d_rec, h, tot, hipMemcpyHostToDevice, D.stream));
+  if (mtot) ECHK(hipMemcpyAsync(D.d_msg.p, hm, mtot, hipMemcpyHostToDevice, D.stream));
   const int nb = (int)((n + 255) / 256);
   ECHK(hipEventRecord(D.ev[0], D.stream));
-  k_ecdsa_digest<<<nb, 256, 0, D.stream>>>((int)n, D.d_msg, doff, dlen, dst, de);
+  k_ecdsa_digest<<<nb, 256, 0, D.stream>>>((int)n, D.d_msg.as<uint8_t>(), doff, dlen, dst, de);
   ECHK(hipGetLastError());
   ECHK(hipEventRecord(D.ev[1], D.stream));
   k_ecdsa_verify<<<nb, 256, 0, D.stream>>>((int)n, drec, de, D.d_table, dst);
@@ -487,9 +442,10 @@ int fts_ecdsa_verify_batch(int device, size_t n, const fts_ecdsa_item* items, in
 
 int fts_ecdsa_last_timings(int device, float* ms2) {
   if (device < 0 || device >= 16 || !ms2) return FTS_API_EINVAL;
-  std::lock_guard<std::mutex> l(g_dev[device].mu);
-  ms2[0] = g_dev[device].ms[0];
-  ms2[1] = g_dev[device].ms[1];
+  DevState& G = dev_state(device);
+  std::lock_guard<std::mutex> l(G.ring.mu);
+  ms2[0] = G.ms[0];
+  ms2[1] = G.ms[1];
   return FTS_API_OK;
 }
 

@@ -27,6 +27,7 @@
 #include "device/prove.hpp"
 #include "host/bn254_host.hpp"
 #include "host/der.hpp"
+#include "host/hip_owned.hpp"
 #include "host/pp_parse.hpp"
 #include "host/request_parse.hpp"
 #include "host/proofs.hpp"
@@ -113,56 +114,19 @@ using namespace fts::host;
 
 namespace {
 
-// growable device buffer
-struct DBuf {
-  void* p = nullptr;
-  size_t cap = 0;
-  // grows geometrically: hipFree synchronises the whole device, so a buffer
-  // must not be re-allocated on every slightly larger batch
-  int ensure(size_t bytes) {
-    if (bytes <= cap) return 0;
-    if (p) hipFree(p);
-    p = nullptr;
-    const size_t grown = cap + cap / 2;
-    cap = 0;
-    size_t want = std::max<size_t>(std::max(bytes, grown), 256);
-    if (hipMalloc(&p, want) != hipSuccess) return -1;
-    cap = want;
-    return 0;
-  }
-  void release() {
-    if (p) hipFree(p);
-    p = nullptr;
-    cap = 0;
-  }
-  template <class T>
-  T* as() const {
-    return reinterpret_cast<T*>(p);
-  }
-};
-
 struct Workspace {
-  DBuf pts, ch, small, hpj, hpa, hpbe, x0, x0mid, terms, scratch, ypow, svec, zvec, rp_excl;
+  DevBuf pts, ch, small, hpj, hpa, hpbe, x0, x0mid, terms, scratch, ypow, svec, zvec, rp_excl;
   // random-linear-combination check + MSM
-  DBuf r_key, r_msc, r_coef, r_colsum, r_fixed, r_flag, r_gcol, r_gfix, r_sel, r_next, r_cnt, m_keys,
+  DevBuf r_key, r_msc, r_coef, r_colsum, r_fixed, r_flag, r_gcol, r_gfix, r_sel, r_next, r_cnt, m_keys,
       m_counts, m_offsets, m_cursor, m_sorted, m_buckets, m_segs, m_wins, m_out, m_scratch, m_win, m_choff, m_chbkt, m_partials;
-  DBuf r_msel, r_mcol, r_mfix, r_mqfix, r_mflag;  // the per-caller-batch combination of a coalesced pass
-  DBuf r_loc, r_save;  // the single-fault locator: located proof, the failed combination S
+  DevBuf r_msel, r_mcol, r_mfix, r_mqfix, r_mflag;  // the per-caller-batch combination of a coalesced pass
+  DevBuf r_loc, r_save;  // the single-fault locator: located proof, the failed combination S
   // action (transfer / issue) batches
-  DBuf rp_raw, rp_sc, rp_status, rp_ipa;
-  DBuf s_act, s_raw, s_owner, s_pts, s_sc, s_status, s_work, s_terms, s_aff, s_affoff, s_msgs, s_jac, s_scratch;
-  DBuf open_rec;  // token opening checks: [raw n*64][scalars n*96][status n*4]
-  DBuf pv;        // batched prover: one arena (prove_arena)
-  DBuf sp;        // sigma provers: one arena
-  void release() {
-    for (DBuf* b : {&open_rec, &pv, &sp, &pts, &ch, &small, &hpj, &hpa, &hpbe, &x0, &x0mid, &terms, &scratch, &ypow, &svec, &zvec, &rp_excl, &rp_raw, &rp_sc, &m_choff, &m_chbkt, &m_partials,
-                    &rp_status, &rp_ipa, &s_act, &s_raw, &s_owner, &s_pts, &s_sc, &s_status, &s_work, &s_terms, &s_aff,
-                    &s_affoff, &s_msgs, &s_jac, &s_scratch, &r_key, &r_msc, &r_coef, &r_colsum, &r_fixed, &r_flag, &r_gcol, &r_gfix,
-                    &r_sel, &r_next, &r_cnt, &r_msel, &r_mcol, &r_mfix, &r_mqfix, &r_mflag, &r_loc, &r_save,
-                    &m_keys, &m_counts, &m_offsets, &m_cursor, &m_sorted, &m_buckets, &m_segs, &m_wins, &m_out,
-                    &m_scratch, &m_win})
-      b->release();
-  }
+  DevBuf rp_raw, rp_sc, rp_status, rp_ipa;
+  DevBuf s_act, s_raw, s_owner, s_pts, s_sc, s_status, s_work, s_terms, s_aff, s_affoff, s_msgs, s_jac, s_scratch;
+  DevBuf open_rec;  // token opening checks: [raw n*64][scalars n*96][status n*4]
+  DevBuf pv;        // batched prover: one arena (prove_arena)
+  DevBuf sp;        // sigma provers: one arena
 };
 
 
@@ -183,7 +147,7 @@ struct Lane {
   // instead of spinning (a spinning waiter per lane burns the process's CPU
   // quota; on a CFS-throttled box that stalls every host thread for ~50 ms
   // out of each 100 ms period)
-  hipEvent_t done = nullptr;
+  Event done;
   hipError_t sync() {
     hipError_t e = hipEventRecord(done, s);
     return e == hipSuccess ? hipEventSynchronize(done) : e;
@@ -193,10 +157,10 @@ struct Lane {
   // only then does a small pass take the latency path (k_rp_fixed_all), which does
   // more total work than the work path and pays off only on an otherwise idle device
   bool alone = true;
-  hipStream_t s = nullptr, s2 = nullptr;
-  hipStream_t s3 = nullptr;         // sigma proofs of action batches (beside the range-proof pass)
-  hipStream_t s4 = nullptr;         // the batch check's x0-free columns beside its MSM
-  hipEvent_t ev_a = nullptr, ev_b = nullptr, ev_c = nullptr, ev_d = nullptr, ev_e = nullptr;  // cross-stream ordering (no timing)
+  Stream s, s2;
+  Stream s3;  // sigma proofs of action batches (beside the range-proof pass)
+  Stream s4;  // the batch check's x0-free columns beside its MSM
+  Event ev_a, ev_b, ev_c, ev_d, ev_e;  // cross-stream ordering (no timing)
   Workspace ws;
   Timeline tl;
   float host_prep_ms = 0, host_enqueue_ms = 0, host_wait_ms = 0;  // host wall time of the last run
@@ -212,60 +176,38 @@ struct Lane {
     MsmWindow win[MSM_WIN_SLOTS][MSM_MAX_WINDOWS];
     int32_t flag;
     int32_t gflag[RP_GATHER_MAX];  // per caller batch of a grouped pass: its combination closed
-  }* pin = nullptr;
-  int32_t* pin_status = nullptr;
-  size_t pin_status_cap = 0;
-  // action batches: pinned staging of the assembled sigma / range-proof inputs
-  uint8_t* stage = nullptr;
-  size_t stage_cap = 0;
-  uint8_t* stage_buf(size_t bytes) {
-    if (bytes > stage_cap) {
-      if (stage) (void)hipHostFree(stage);
-      stage = nullptr;
-      const size_t want = std::max<size_t>(std::max(bytes, stage_cap + stage_cap / 2), 1 << 20);
-      stage_cap = 0;
-      if (hipHostMalloc((void**)&stage, want, 0) != hipSuccess) return nullptr;
-      stage_cap = want;
-    }
-    return stage;
+  }* pin = nullptr;  // view of pin_mem
+  PinBuf pin_mem, pin_status;
+  int32_t* status_buf(size_t n) {
+    return pin_status.reserve(std::max<size_t>(n, 4096) * 4) ? pin_status.as<int32_t>() : nullptr;
   }
+  // action batches: pinned staging of the assembled sigma / range-proof inputs
+  PinBuf stage;
+  uint8_t* stage_buf(size_t bytes) { return stage.grow(bytes, 1 << 20) ? stage.as<uint8_t>() : nullptr; }
   // pinned source of the per-caller-batch slot map (its own buffer: `stage` may still
   // be the source of an action batch's pending uploads)
-  int32_t* pin_sel = nullptr;
-  size_t pin_sel_cap = 0;
+  PinBuf pin_sel;
   int32_t* sel_buf(size_t n) {
-    if (n > pin_sel_cap) {
-      if (pin_sel) (void)hipHostFree(pin_sel);
-      pin_sel = nullptr;
-      pin_sel_cap = 0;
-      const size_t want = std::max<size_t>(n, 1 << 16);
-      if (hipHostMalloc((void**)&pin_sel, want * 4, 0) != hipSuccess) return nullptr;
-      pin_sel_cap = want;
-    }
-    return pin_sel;
+    return pin_sel.reserve(std::max<size_t>(n, 1 << 16) * 4) ? pin_sel.as<int32_t>() : nullptr;
   }
-  int32_t* status_buf(size_t n) {
-    if (n > pin_status_cap) {
-      if (pin_status) (void)hipHostFree(pin_status);
-      pin_status = nullptr;
-      pin_status_cap = 0;
-      if (hipHostMalloc((void**)&pin_status, std::max<size_t>(n, 4096) * 4, 0) != hipSuccess) return nullptr;
-      pin_status_cap = std::max<size_t>(n, 4096);
-    }
-    return pin_status;
+  // streams, completion event, pinned block and timeline; FTS_API_OK or the error
+  int create(int prio_hi) {
+    if (s.create() != hipSuccess || done.create(hipEventBlockingSync | hipEventDisableTiming) != hipSuccess)
+      return FTS_API_EDEVICE;
+    if (!pin_mem.reserve(sizeof(Pinned))) return FTS_API_ENOMEM;
+    pin = pin_mem.as<Pinned>();
+    if (s2.create() != hipSuccess || s4.create() != hipSuccess || s3.create(prio_hi) != hipSuccess) return FTS_API_EDEVICE;
+    for (Event* e : {&ev_a, &ev_b, &ev_c, &ev_d, &ev_e})
+      if (e->create(hipEventDisableTiming) != hipSuccess) return FTS_API_EDEVICE;
+    tl.create();
+    return FTS_API_OK;
   }
-  void free_pinned() {
-    if (pin) (void)hipHostFree(pin);
-    if (pin_status) (void)hipHostFree(pin_status);
-    if (pin_sel) (void)hipHostFree(pin_sel);
-    pin_sel = nullptr;
-    pin_sel_cap = 0;
-    if (stage) (void)hipHostFree(stage);
-    pin = nullptr;
-    pin_status = nullptr;
-    pin_status_cap = 0;
-    stage = nullptr;
-    stage_cap = 0;
+  Lane() = default;
+  // drains the lane's streams before any member (workspace, pinned buffers) is released
+  ~Lane() {
+    for (hipStream_t x : {(hipStream_t)s, (hipStream_t)s2, (hipStream_t)s4, (hipStream_t)s3})
+      if (x) hipStreamSynchronize(x);
+    tl.destroy();
   }
 };
 // host worker threads for batch parsing: the CPUs this process may actually
@@ -375,6 +317,36 @@ static inline double now_ms() {
 }
 
 struct ActSlot;
+struct fts_rp_batch {
+  int B = 0;
+  int device = 0;
+  // staged on a multi-device context: one child batch per shard, shard j holds
+  // proofs [bounds[j], bounds[j+1]) of the caller's batch
+  std::vector<fts_rp_batch*> parts;
+  std::vector<fts_ctx*> part_ctx;
+  std::vector<size_t> bounds;
+  int merged = 1;  // batches in the device pass that verified it last
+  bool dense = false;  // its last failed verification found dense bad proofs (FTS_GT_ADAPT)
+  int locate_skip = 0, locate_backoff = 8;  // single-fault locator backoff (fts_ctx::locate)
+  // timings of this batch's last verification
+  int ntim = 0;
+  const char* tim_name[Timeline::CAP];
+  float tim_ms[Timeline::CAP];
+  double tim_work[Timeline::CAP];
+  ~fts_rp_batch() {
+    for (fts_rp_batch* q : parts) delete q;
+    if (raw_mem.p) hipSetDevice(device);
+  }
+  // a staged batch owns its records; a staging slot's batch has empty owners and its
+  // views below point into the slot's `dev`
+  DevBuf raw_mem, sc_mem, status0_mem, status_mem, ipa_mem;
+  uint8_t* raw = nullptr;
+  uint32_t* sc = nullptr;
+  int32_t* status0 = nullptr;  // host-parse verdicts (restored before every run)
+  int32_t* status = nullptr;
+  int32_t* ipa_flag = nullptr;
+};
+
 // One call waiting for (or being served by) a device pass: a staged range-proof
 // batch (fts_rp_batch_verify, fts_rp_verify_batch), or an action call (transfers /
 // issues / requests) whose range proofs are `b` and whose sigma batch is `act`.
@@ -408,6 +380,30 @@ struct ActionState {
 };
 }  // namespace
 
+// Staging slot of fts_rp_verify_batch (host DER bytes -> device), and the base of the
+// action calls' ActSlot: pinned host records and device input buffers, grown
+// geometrically and reused across calls, so a call neither allocates nor frees
+// device memory (hipFree synchronises the whole device, stalling every other
+// lane's pass)
+struct StageSlot {
+  std::unique_ptr<fts_rp_batch> b;  // its views point into `dev` (not owned by the batch)
+  PinBuf pin;
+  DevBuf dev;
+  Stream s;
+  Event done;  // blocking-sync: the waiting caller sleeps
+  bool create(int device) {
+    b.reset(new fts_rp_batch());
+    b->device = device;
+    return s.create() == hipSuccess && done.create(hipEventBlockingSync | hipEventDisableTiming) == hipSuccess;
+  }
+  bool size(size_t pin_bytes, size_t dev_bytes) { return pin.grow(pin_bytes, 0) && dev.grow(dev_bytes, 0); }
+  StageSlot() = default;
+  ~StageSlot() {  // the stream may still read pin / dev
+    if (s) hipStreamSynchronize(s);
+  }
+};
+using RpSlot = StageSlot;
+
 // An action call staged for the dispatcher (act_stage), pooled per context like
 // RpSlot: the call's records parsed straight into pinned host memory in their
 // device layout, one upload into `dev`, and the call's sigma workspace behind
@@ -419,17 +415,10 @@ struct ActionState {
 // issue / request calls share passes instead of taking a lane each, and the sigma
 // work overlaps other passes instead of sitting on a pass's critical path
 // (DESIGN.md §3.4).
-struct ActSlot {
-  fts_rp_batch* b = nullptr;  // the call's range proofs: raw / sc / status0 / ipa point into `dev`
-  uint8_t* pin = nullptr;
-  size_t pin_cap = 0;
-  uint8_t* dev = nullptr;
-  size_t dev_cap = 0;
-  hipStream_t s = nullptr;
-  hipEvent_t done = nullptr;   // blocking-sync: the staging caller sleeps
+struct ActSlot : StageSlot {
   // on s: [0] before the sigma kernels, [1] after decode + primes + V slots, [2] after
   // the sigma equations (the pass waits for it before gathering the range proofs)
-  hipEvent_t ev_sig[3] = {nullptr, nullptr, nullptr};
+  Event ev_sig[3];
   SigBatchDev sd{};            // the call's sigma batch (sd.A == 0: none); rp_raw = the slot's range proofs
   int32_t* sig_res = nullptr;  // pinned: sigma verdicts [sd.A], downloaded by the pass
   std::vector<int32_t> rp_res;  // range-proof verdicts [b->B], scattered by the pass
@@ -439,39 +428,25 @@ struct ActSlot {
   float phase_ms[3] = {0, 0, 0};  // act_stage's shapes / layout / decode steps of the last call
 };
 
-// fts_rp_verify_batch staging slot (host DER bytes -> device): pinned host
-// records and device input buffers, grown geometrically and reused across
-// calls, so a call neither allocates nor frees device memory (hipFree
-// synchronises the whole device, stalling every other lane's pass)
-struct RpSlot {
-  fts_rp_batch* b = nullptr;  // device pointers into `dev` (not owned by the batch)
-  uint8_t* pin = nullptr;
-  size_t pin_cap = 0;
-  uint8_t* dev = nullptr;
-  size_t dev_cap = 0;
-  hipStream_t s = nullptr;
-  hipEvent_t done = nullptr;  // blocking-sync: the waiting caller sleeps
-};
-
 struct fts_ctx {
   int device = 0;
   // multi-device context (fts_ctx_create_devices): one child context per device;
   // batch entry points shard their batch over the children (multi_* below)
-  std::vector<fts_ctx*> shards;
+  std::vector<fts_ctx*> shards;  // owned (released by the destructor)
   PublicParams pp;
   int n = 0, k = 0;
-  uint32_t* d_tables = nullptr;
-  uint32_t* d_wtables = nullptr;  // wide tables of [H_0 .. H_{n-1}, K, P] (k_rp_fixed_exact)
+  DevBuf d_tables;
+  DevBuf d_wtables;  // wide tables of [H_0 .. H_{n-1}, K, P] (k_rp_fixed_exact)
   // their window width: 22 bits (12 additions per product, 1.5 GiB per base) when the
   // device has the memory at context creation, else 20 (13, 436 MiB); FTS_WIDE_BITS
   int wbits = 20;
   int wbits_forced = 0;  // fts_ctx_opts.wide_bits / FTS_WIDE_BITS: no fallback to 20 bits
   int nlanes = 0;
-  uint8_t* d_x0const = nullptr;
-  uint8_t* d_x0tmpl = nullptr;  // x0 message blocks [x0_cb0, x0_cb1): shared by every proof
+  DevBuf d_x0const;
+  DevBuf d_x0tmpl;  // x0 message blocks [x0_cb0, x0_cb1): shared by every proof
   size_t table_bytes = 0;
   // lane pool
-  std::vector<Lane*> lanes;
+  std::vector<std::unique_ptr<Lane>> lanes;
   std::vector<int> free_lanes;
   std::mutex mu;
   std::condition_variable cv;
@@ -575,7 +550,7 @@ struct fts_ctx {
   // (device-side event chain under fx_mu), staggering concurrent passes
   int fx_serial = 0;
   std::mutex fx_mu;
-  hipEvent_t fx_last = nullptr;  // the fixed-base event of the pass enqueued last
+  hipEvent_t fx_last = nullptr;  // (a lane's ev_d, not owned) the fixed-base event of the pass enqueued last
   // FTS_RLC_FORK: the batch check forks after the fixed-base products (1) or after the
   // challenges (0); 2 (default): after the challenges on the latency path (a lone small
   // pass: its MSM chain is the critical path, 3.16 -> 2.98 ms per 4,096-proof batch),
@@ -591,8 +566,17 @@ struct fts_ctx {
   std::once_flag prover_once;
   ProverTables ptab;
   std::mutex slot_mu;
-  std::vector<RpSlot*> slots, free_slots;  // fts_rp_verify_batch staging (all / idle)
-  std::vector<ActSlot*> aslots, free_aslots;  // action-call staging (all / idle), under slot_mu
+  std::vector<std::unique_ptr<RpSlot>> slots;    // fts_rp_verify_batch staging
+  std::vector<std::unique_ptr<ActSlot>> aslots;  // action-call staging
+  std::vector<RpSlot*> free_slots;               // the idle ones, under slot_mu
+  std::vector<ActSlot*> free_aslots;
+  // members are released on the context's device; a host-only context and a
+  // multi-device parent own no device resource
+  ~fts_ctx() {
+    const bool owns_device = shards.empty() && device != FTS_DEVICE_NONE && !lanes.empty();
+    for (fts_ctx* ch : shards) delete ch;
+    if (owns_device) hipSetDevice(device);
+  }
 };
 
 // RAII lane acquisition (want < 0: any free lane)
@@ -606,7 +590,7 @@ struct LaneGuard {
       return std::find(c->free_lanes.begin(), c->free_lanes.end(), want) != c->free_lanes.end();
     });
     auto it = want < 0 ? c->free_lanes.end() - 1 : std::find(c->free_lanes.begin(), c->free_lanes.end(), want);
-    L = c->lanes[*it];
+    L = c->lanes[*it].get();
     c->free_lanes.erase(it);
     L->alone = c->free_lanes.size() + 1 == c->lanes.size();
   }
@@ -615,29 +599,6 @@ struct LaneGuard {
     c->free_lanes.push_back(L->id);
     c->wake_lane_waiters();
   }
-};
-
-struct fts_rp_batch {
-  int B = 0;
-  int device = 0;
-  // staged on a multi-device context: one child batch per shard, shard j holds
-  // proofs [bounds[j], bounds[j+1]) of the caller's batch
-  std::vector<fts_rp_batch*> parts;
-  std::vector<fts_ctx*> part_ctx;
-  std::vector<size_t> bounds;
-  int merged = 1;  // batches in the device pass that verified it last
-  bool dense = false;  // its last failed verification found dense bad proofs (FTS_GT_ADAPT)
-  int locate_skip = 0, locate_backoff = 8;  // single-fault locator backoff (fts_ctx::locate)
-  // timings of this batch's last verification
-  int ntim = 0;
-  const char* tim_name[Timeline::CAP];
-  float tim_ms[Timeline::CAP];
-  double tim_work[Timeline::CAP];
-  uint8_t* raw = nullptr;
-  uint32_t* sc = nullptr;
-  int32_t* status0 = nullptr;  // host-parse verdicts (restored before every run)
-  int32_t* status = nullptr;
-  int32_t* ipa_flag = nullptr;
 };
 
 namespace fts {
@@ -667,18 +628,14 @@ static int ctx_create(const uint8_t* pp_bytes, size_t pp_len, uint32_t bits, int
                       const fts_ctx_opts* opts = nullptr) {
   if (!pp_bytes || !out) return FTS_API_EINVAL;
   *out = nullptr;
-  fts_ctx* c = new fts_ctx();
+  std::unique_ptr<fts_ctx> c(new fts_ctx());  // released (on its device) by every failing exit
   std::string err;
   if (!parse_public_params(pp_bytes, pp_len, c->pp, err)) {
     fprintf(stderr, "fts_gpu: public parameters rejected: %s\n", err.c_str());
-    delete c;
     return FTS_API_EPP;
   }
   if (bits) {
-    if (bits > c->pp.bit_length || (bits & (bits - 1)) || bits < 2) {
-      delete c;
-      return FTS_API_ESIZE;
-    }
+    if (bits > c->pp.bit_length || (bits & (bits - 1)) || bits < 2) return FTS_API_ESIZE;
     c->pp.left.resize(bits);
     c->pp.right.resize(bits);
     c->pp.bit_length = bits;
@@ -690,35 +647,14 @@ static int ctx_create(const uint8_t* pp_bytes, size_t pp_len, uint32_t bits, int
   c->k = (int)c->pp.rounds;
   if (device == FTS_DEVICE_NONE) {  // host-only context: parsing + prover, no GPU
     c->device = FTS_DEVICE_NONE;
-    *out = c;
+    *out = c.release();
     return FTS_API_OK;
   }
   if (device < 0) {
     if (hipGetDevice(&device) != hipSuccess) device = 0;
   }
   c->device = device;
-  auto fail = [&](int code) {
-    for (Lane* L : c->lanes) {
-      if (L->s3) hipStreamDestroy(L->s3);
-      if (L->ev_a) hipEventDestroy(L->ev_a);
-      if (L->ev_b) hipEventDestroy(L->ev_b);
-      if (L->ev_c) hipEventDestroy(L->ev_c);
-      if (L->ev_d) hipEventDestroy(L->ev_d);
-      if (L->ev_e) hipEventDestroy(L->ev_e);
-      if (L->s2 && L->s2 != L->s) hipStreamDestroy(L->s2);
-      if (L->s4 && L->s4 != L->s) hipStreamDestroy(L->s4);
-      if (L->s) hipStreamDestroy(L->s);
-      L->tl.destroy();
-      if (L->done) hipEventDestroy(L->done);
-      L->free_pinned();
-      delete L;
-    }
-    if (c->d_tables) hipFree(c->d_tables);
-    if (c->d_wtables) hipFree(c->d_wtables);
-    delete c;
-    return code;
-  };
-  if (hipSetDevice(device) != hipSuccess) return fail(FTS_API_EDEVICE);
+  if (hipSetDevice(device) != hipSuccess) return FTS_API_EDEVICE;
   int nl = 4;  // lanes (FTS_LANES): 4 beat 5 and 3 on the burst and the steady state (s20_sweep4.sh)
   if (const char* e = getenv("FTS_LANES")) nl = std::max(1, std::min(16, atoi(e)));
   if (opts && opts->lanes > 0) nl = std::min(16, opts->lanes);
@@ -753,7 +689,7 @@ static int ctx_create(const uint8_t* pp_bytes, size_t pp_len, uint32_t bits, int
     if (const char* e = getenv("FTS_WAVE_PRIO"))
       for (int i = 0; i < PS_N && e[i]; i++)
         if (e[i] >= '0' && e[i] <= '3') pr[i] = e[i] - '0';
-    if (rp_set_wave_prio(pr) != hipSuccess || msm_set_wave_prio(pr) != hipSuccess) return fail(FTS_API_EDEVICE);
+    if (rp_set_wave_prio(pr) != hipSuccess || msm_set_wave_prio(pr) != hipSuccess) return FTS_API_EDEVICE;
   }
   // the batch check's stream (s3: RLC weights + MSM, the longest chain of a small
   // pass) gets the device's highest stream priority, so its few waves are
@@ -761,25 +697,10 @@ static int ctx_create(const uint8_t* pp_bytes, size_t pp_len, uint32_t bits, int
   int prio_lo = 0, prio_hi = 0;
   if (hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi) != hipSuccess) prio_lo = prio_hi = 0;
   for (int i = 0; i < nl; i++) {
-    Lane* L = new Lane();
-    L->id = i;
-    c->lanes.push_back(L);
+    c->lanes.emplace_back(new Lane());
+    c->lanes.back()->id = i;
     c->free_lanes.push_back(i);
-    if (hipStreamCreateWithFlags(&L->s, hipStreamNonBlocking) != hipSuccess) return fail(FTS_API_EDEVICE);
-    if (hipEventCreateWithFlags(&L->done, hipEventBlockingSync | hipEventDisableTiming) != hipSuccess)
-      return fail(FTS_API_EDEVICE);
-    if (hipHostMalloc((void**)&L->pin, sizeof(Lane::Pinned), 0) != hipSuccess) return fail(FTS_API_ENOMEM);
-    if (hipStreamCreateWithFlags(&L->s2, hipStreamNonBlocking) != hipSuccess ||
-        hipStreamCreateWithFlags(&L->s4, hipStreamNonBlocking) != hipSuccess)
-      return fail(FTS_API_EDEVICE);
-    if (hipStreamCreateWithPriority(&L->s3, hipStreamNonBlocking, prio_hi) != hipSuccess ||
-        hipEventCreateWithFlags(&L->ev_a, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&L->ev_b, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&L->ev_c, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&L->ev_d, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&L->ev_e, hipEventDisableTiming) != hipSuccess)
-      return fail(FTS_API_EDEVICE);
-    L->tl.create();
+    if (int rc = c->lanes.back()->create(prio_hi)) return rc;
   }
   hipStream_t s0 = c->lanes[0]->s;
   const int n = c->n;
@@ -805,20 +726,18 @@ static int ctx_create(const uint8_t* pp_bytes, size_t pp_len, uint32_t bits, int
       memcpy(&hb[b * 16], bases[b].x.v, 32);  // 4x64 LE == 8x32 LE Montgomery form
       memcpy(&hb[b * 16 + 8], bases[b].y.v, 32);
     }
-  uint32_t* d_bases = nullptr;
-  uint32_t* d_scr = nullptr;
+  // build temporaries: s0 is drained before any exit below releases them
+  DevBuf bases_buf, scr_buf;
   c->table_bytes = (size_t)nb * fb_words_per_base() * 4;
-  if (hipMalloc(&c->d_tables, c->table_bytes) != hipSuccess) return fail(FTS_API_ENOMEM);
-  if (hipMalloc(&d_bases, hb.size() * 4) != hipSuccess) return fail(FTS_API_ENOMEM);
   const int chunk = std::min(nb, 16);  // bases per build pass (bounds the Jacobian scratch)
-  if (hipMalloc(&d_scr, table_build_scratch_bytes(chunk)) != hipSuccess) {
-    hipFree(d_bases);
-    return fail(FTS_API_ENOMEM);
-  }
+  if (!c->d_tables.reserve(c->table_bytes) || !bases_buf.reserve(hb.size() * 4) ||
+      !scr_buf.reserve(table_build_scratch_bytes(chunk)))
+    return FTS_API_ENOMEM;
+  uint32_t* const d_bases = bases_buf.as<uint32_t>();
   hipMemcpyAsync(d_bases, hb.data(), hb.size() * 4, hipMemcpyHostToDevice, s0);
   for (int b0 = 0; b0 < nb; b0 += chunk)
-    launch_build_tables(d_bases + (size_t)b0 * 16, std::min(chunk, nb - b0), c->d_tables + (size_t)b0 * fb_words_per_base(),
-                        d_scr, s0);
+    launch_build_tables(d_bases + (size_t)b0 * 16, std::min(chunk, nb - b0),
+                        c->d_tables.as<uint32_t>() + (size_t)b0 * fb_words_per_base(), scr_buf.as<uint32_t>(), s0);
   // wide tables of the per-proof bases H_i, K, P (same build, wider windows):
   // 22-bit windows (one mixed addition fewer per product: -8 % of the pass's
   // largest kernel) when the free HBM holds them with room to spare for the lanes'
@@ -856,41 +775,31 @@ static int ctx_create(const uint8_t* pp_bytes, size_t pp_len, uint32_t bits, int
       const int src = i < n ? n + i : (i == n ? 2 * n + 4 : 2 * n + 2);  // H_i, K, P in `bases`
       memcpy(&hw[(size_t)i * 16], &hb[(size_t)src * 16], 64);
     }
-    uint32_t* d_wb = nullptr;
-    uint32_t* d_wscr = nullptr;
+    DevBuf wb_buf, wscr_buf;
     int wchunk = 1;
     for (;;) {  // 22-bit tables that do not fit after all (other contexts' lanes): 20-bit
       wchunk = std::min(nw, c->wbits == 22 ? 1 : 4);  // bounds the Jacobian build scratch (2.4 / 1.6 GB)
-      if (hipMalloc(&c->d_wtables, (size_t)nw * fbw_words_per_base(c->wbits) * 4) == hipSuccess &&
-          hipMalloc(&d_wb, hw.size() * 4) == hipSuccess &&
-          hipMalloc(&d_wscr, wide_build_scratch_bytes(wchunk, c->wbits)) == hipSuccess)
+      if (c->d_wtables.reserve((size_t)nw * fbw_words_per_base(c->wbits) * 4) && wb_buf.reserve(hw.size() * 4) &&
+          wscr_buf.reserve(wide_build_scratch_bytes(wchunk, c->wbits)))
         break;
-      if (d_wb) hipFree(d_wb);
-      if (c->d_wtables) hipFree(c->d_wtables);
-      d_wb = nullptr;
-      c->d_wtables = nullptr;
+      wb_buf.release();
+      c->d_wtables.release();
       (void)hipGetLastError();
       if (c->wbits == 22 && !c->wbits_forced) {
         c->wbits = 20;
         continue;
       }
-      hipFree(d_bases);
-      hipFree(d_scr);
-      return fail(FTS_API_ENOMEM);
+      (void)hipStreamSynchronize(s0);
+      return FTS_API_ENOMEM;
     }
+    uint32_t* const d_wb = wb_buf.as<uint32_t>();
     hipMemcpyAsync(d_wb, hw.data(), hw.size() * 4, hipMemcpyHostToDevice, s0);
     for (int b0 = 0; b0 < nw; b0 += wchunk)
       launch_build_wide_tables(d_wb + (size_t)b0 * 16, std::min(wchunk, nw - b0),
-                               c->d_wtables + (size_t)b0 * fbw_words_per_base(c->wbits), d_wscr, s0, c->wbits);
+                               c->d_wtables.as<uint32_t>() + (size_t)b0 * fbw_words_per_base(c->wbits),
+                               wscr_buf.as<uint32_t>(), s0, c->wbits);
     c->table_bytes += (size_t)nw * fbw_words_per_base(c->wbits) * 4;
-    hipError_t we = hipStreamSynchronize(s0);
-    hipFree(d_wb);
-    hipFree(d_wscr);
-    if (we != hipSuccess) {
-      hipFree(d_bases);
-      hipFree(d_scr);
-      return fail(FTS_API_EDEVICE);
-    }
+    if (hipStreamSynchronize(s0) != hipSuccess) return FTS_API_EDEVICE;
   }
   // constant part of the x0 transcript: hex(G_i) "||" ... hex(Q) "||"
   std::string xc;
@@ -900,21 +809,19 @@ static int ctx_create(const uint8_t* pp_bytes, size_t pp_len, uint32_t bits, int
     xc += hex_of(b, 64);
     xc += "||";
   }
-  if (hipMalloc(&c->d_x0const, xc.size()) != hipSuccess) return fail(FTS_API_ENOMEM);
-  hipMemcpyAsync(c->d_x0const, xc.data(), xc.size(), hipMemcpyHostToDevice, s0);
+  if (!c->d_x0const.reserve(xc.size())) return FTS_API_ENOMEM;
+  hipMemcpyAsync(c->d_x0const.p, xc.data(), xc.size(), hipMemcpyHostToDevice, s0);
   // block-aligned template of the fully constant SHA-256 blocks of the x0 message
   std::string xt(64u * (x0_cb1(n) - x0_cb0(n)), '\0');
   for (size_t j = 0; j < xt.size(); j++) xt[j] = xc[64u * x0_cb0(n) + j - x0_const_off(n)];
-  if (hipMalloc(&c->d_x0tmpl, xt.size()) != hipSuccess) return fail(FTS_API_ENOMEM);
-  hipMemcpyAsync(c->d_x0tmpl, xt.data(), xt.size(), hipMemcpyHostToDevice, s0);
+  if (!c->d_x0tmpl.reserve(xt.size())) return FTS_API_ENOMEM;
+  hipMemcpyAsync(c->d_x0tmpl.p, xt.data(), xt.size(), hipMemcpyHostToDevice, s0);
   hipError_t e = hipStreamSynchronize(s0);
-  hipFree(d_bases);
-  hipFree(d_scr);
   if (e != hipSuccess) {
     fprintf(stderr, "fts_gpu: table build failed: %s\n", hipGetErrorString(e));
-    return fail(FTS_API_EDEVICE);
+    return FTS_API_EDEVICE;
   }
-  *out = c;
+  *out = c.release();
   return FTS_API_OK;
 }
 
@@ -1040,61 +947,7 @@ int fts_ctx_create_bits(const uint8_t* pp, size_t pp_len, uint32_t bit_length, i
   return ctx_create(pp, pp_len, bit_length, device, out);
 }
 
-void fts_ctx_destroy(fts_ctx* c) {
-  if (!c) return;
-  for (fts_ctx* ch : c->shards) fts_ctx_destroy(ch);
-  c->shards.clear();
-  if (c->device == FTS_DEVICE_NONE || c->lanes.empty()) {
-    delete c;
-    return;
-  }
-  hipSetDevice(c->device);
-  for (Lane* L : c->lanes) {
-    if (L->s) hipStreamSynchronize(L->s);
-    if (L->s2 && L->s2 != L->s) hipStreamSynchronize(L->s2);
-    if (L->s4 && L->s4 != L->s) hipStreamSynchronize(L->s4);
-    if (L->s3) hipStreamSynchronize(L->s3);
-    L->ws.release();
-    if (L->s3) hipStreamDestroy(L->s3);
-    if (L->ev_a) hipEventDestroy(L->ev_a);
-    if (L->ev_b) hipEventDestroy(L->ev_b);
-    if (L->ev_c) hipEventDestroy(L->ev_c);
-    if (L->ev_d) hipEventDestroy(L->ev_d);
-    if (L->ev_e) hipEventDestroy(L->ev_e);
-    L->tl.destroy();
-    if (L->done) hipEventDestroy(L->done);
-    if (L->s2 && L->s2 != L->s) hipStreamDestroy(L->s2);
-    if (L->s4 && L->s4 != L->s) hipStreamDestroy(L->s4);
-    if (L->s) hipStreamDestroy(L->s);
-    L->free_pinned();
-    delete L;
-  }
-  if (c->d_tables) hipFree(c->d_tables);
-  if (c->d_wtables) hipFree(c->d_wtables);
-  if (c->d_x0const) hipFree(c->d_x0const);
-  if (c->d_x0tmpl) hipFree(c->d_x0tmpl);
-  for (RpSlot* sl : c->slots) {
-    if (sl->s) hipStreamSynchronize(sl->s);
-    if (sl->dev) hipFree(sl->dev);
-    if (sl->pin) (void)hipHostFree(sl->pin);
-    if (sl->done) hipEventDestroy(sl->done);
-    if (sl->s) hipStreamDestroy(sl->s);
-    delete sl->b;
-    delete sl;
-  }
-  for (ActSlot* sl : c->aslots) {
-    if (sl->s) hipStreamSynchronize(sl->s);
-    if (sl->dev) hipFree(sl->dev);
-    if (sl->pin) (void)hipHostFree(sl->pin);
-    if (sl->done) hipEventDestroy(sl->done);
-    for (hipEvent_t e : sl->ev_sig)
-      if (e) hipEventDestroy(e);
-    if (sl->s) hipStreamDestroy(sl->s);
-    delete sl->b;
-    delete sl;
-  }
-  delete c;
-}
+void fts_ctx_destroy(fts_ctx* c) { delete c; }
 
 int fts_ctx_info(const fts_ctx* c, fts_pp_info* o) {
   if (!c || !o) return FTS_API_EINVAL;
@@ -1258,13 +1111,13 @@ static int msm_prepare(Lane& L, int N, MsmPlan& mp, int slot, int ch, bool local
 // uploaded before the lane's next sync must use different slots (MSM_SLOT_*)
 static int msm_prepare_plan(Lane& L, MsmPlan& mp, int slot) {
   Workspace& w = L.ws;
-  if (w.m_choff.ensure((size_t)mp.NB * 4) || w.m_chbkt.ensure((size_t)mp.NC * 4) ||
-      w.m_partials.ensure((size_t)mp.NC * 96) || w.m_keys.ensure((size_t)mp.nw * mp.NV * 4) ||
-      w.m_counts.ensure((size_t)mp.NB * 4) || w.m_offsets.ensure((size_t)mp.NB * 4) ||
-      w.m_cursor.ensure((size_t)mp.nw * mp.NV * 4) || w.m_sorted.ensure((size_t)mp.nw * mp.NV * 4) ||
-      w.m_buckets.ensure((size_t)mp.NB * 96) || w.m_segs.ensure((size_t)mp.NS * 96) ||
-      w.m_wins.ensure((size_t)(mp.nw + 1) * 96) || w.m_out.ensure((size_t)mp.G * 96) ||
-      w.m_scratch.ensure(std::max((size_t)mp.NS * 96, msm_scratch_words(mp) * 4)) || w.m_win.ensure(sizeof(mp.win)))
+  if (!w.m_choff.grow((size_t)mp.NB * 4) || !w.m_chbkt.grow((size_t)mp.NC * 4) ||
+      !w.m_partials.grow((size_t)mp.NC * 96) || !w.m_keys.grow((size_t)mp.nw * mp.NV * 4) ||
+      !w.m_counts.grow((size_t)mp.NB * 4) || !w.m_offsets.grow((size_t)mp.NB * 4) ||
+      !w.m_cursor.grow((size_t)mp.nw * mp.NV * 4) || !w.m_sorted.grow((size_t)mp.nw * mp.NV * 4) ||
+      !w.m_buckets.grow((size_t)mp.NB * 96) || !w.m_segs.grow((size_t)mp.NS * 96) ||
+      !w.m_wins.grow((size_t)(mp.nw + 1) * 96) || !w.m_out.grow((size_t)mp.G * 96) ||
+      !w.m_scratch.grow(std::max((size_t)mp.NS * 96, msm_scratch_words(mp) * 4)) || !w.m_win.grow(sizeof(mp.win)))
     return FTS_API_ENOMEM;
   mp.d_win = w.m_win.as<MsmWindow>();
   MsmWindow* src = L.pin->win[slot];
@@ -1293,14 +1146,14 @@ static int msm_prepare_plan(Lane& L, MsmPlan& mp, int slot) {
 static int rp_buffers(fts_ctx* c, Lane& L, int B) {
   const int n = c->n, k = c->k, npts = rp_npts(k), N = B * npts;
   Workspace& w = L.ws;
-  if (w.pts.ensure((size_t)B * npts * 64) || w.ch.ensure((size_t)B * rp_nch(k) * 32) ||
-      w.small.ensure((size_t)B * (2 + k) * SMALL_SLOT) || w.hpj.ensure((size_t)B * (n + 1) * 96) ||
-      w.hpa.ensure((size_t)B * (n + 1) * 64) || w.hpbe.ensure((size_t)B * (n + 1) * 64) ||
-      w.x0.ensure((size_t)B * x0_var_bytes(n)) || w.x0mid.ensure((size_t)B * 32) || w.terms.ensure(rp_terms_words(B, n, k) * 4) ||
-      w.scratch.ensure(std::max(rp_scratch_words(B, n, k), (size_t)B * 10 * 24) * 4) || w.r_key.ensure(32) ||
-      w.r_msc.ensure((size_t)N * 32) || w.r_coef.ensure((size_t)B * RLC_NCOEF * 32) ||
-      w.r_colsum.ensure(rlc_ncols(n) * 32 * (1 + 64))  /* + RQ_PARTS partial rows of column Q */ || w.r_fixed.ensure(rlc_ncols(n) * 96) || w.r_flag.ensure(4) || w.ypow.ensure((size_t)B * n * 32) ||
-      w.svec.ensure((size_t)B * n * 32) || w.zvec.ensure((size_t)B * n * 32) || w.rp_excl.ensure((size_t)B * 4) ||
+  if (!w.pts.grow((size_t)B * npts * 64) || !w.ch.grow((size_t)B * rp_nch(k) * 32) ||
+      !w.small.grow((size_t)B * (2 + k) * SMALL_SLOT) || !w.hpj.grow((size_t)B * (n + 1) * 96) ||
+      !w.hpa.grow((size_t)B * (n + 1) * 64) || !w.hpbe.grow((size_t)B * (n + 1) * 64) ||
+      !w.x0.grow((size_t)B * x0_var_bytes(n)) || !w.x0mid.grow((size_t)B * 32) || !w.terms.grow(rp_terms_words(B, n, k) * 4) ||
+      !w.scratch.grow(std::max(rp_scratch_words(B, n, k), (size_t)B * 10 * 24) * 4) || !w.r_key.grow(32) ||
+      !w.r_msc.grow((size_t)N * 32) || !w.r_coef.grow((size_t)B * RLC_NCOEF * 32) ||
+      !w.r_colsum.grow(rlc_ncols(n) * 32 * (1 + 64))  /* + RQ_PARTS partial rows of column Q */ || !w.r_fixed.grow(rlc_ncols(n) * 96) || !w.r_flag.grow(4) || !w.ypow.grow((size_t)B * n * 32) ||
+      !w.svec.grow((size_t)B * n * 32) || !w.zvec.grow((size_t)B * n * 32) || !w.rp_excl.grow((size_t)B * 4) ||
       !L.status_buf((size_t)B))
     return FTS_API_ENOMEM;
   return FTS_API_OK;
@@ -1315,8 +1168,8 @@ static int lane_reserve(fts_ctx* c, Lane& L, int B, bool inputs) {
   if (int rc = msm_prepare(L, B * npts, big, MSM_SLOT_RESERVE, MSM_CH, c->msm_sort != 0, c->msm_maxc)) return rc;
   if (int rc = rp_buffers(c, L, B)) return rc;
   Workspace& w = L.ws;
-  if (inputs && (w.rp_raw.ensure((size_t)B * npts * 64) || w.rp_sc.ensure((size_t)B * RP_NSC * 32) ||
-                 w.rp_status.ensure((size_t)B * 4) || w.rp_ipa.ensure((size_t)B * 4)))
+  if (inputs && (!w.rp_raw.grow((size_t)B * npts * 64) || !w.rp_sc.grow((size_t)B * RP_NSC * 32) ||
+                 !w.rp_status.grow((size_t)B * 4) || !w.rp_ipa.grow((size_t)B * 4)))
     return FTS_API_ENOMEM;
   L.presized = true;
   return FTS_API_OK;
@@ -1362,8 +1215,8 @@ static int rp_group_fallback(fts_ctx* c, Lane& L, const RpBatchDev& d, const Rlc
   const size_t slots = std::max<size_t>(sel_big.size() + sel_small.size(), (size_t)B + RP_GT2);
   // groups of any round: round 1 has sel_big / gt1 + sel_small / RP_GT2, round 2 at most slots / RP_GT2
   const size_t gmax = std::max(sel_big.size() / c->gt1 + sel_small.size() / RP_GT2, (slots + RP_GT2 - 1) / RP_GT2);
-  if (w.r_sel.ensure(2 * slots * 4) || w.r_next.ensure(slots * 4) || w.r_cnt.ensure(8) ||
-      w.r_gcol.ensure(gmax * rlc_ncols(n) * 32) || w.r_gfix.ensure(gmax * rlc_ncols(n) * 96))
+  if (!w.r_sel.grow(2 * slots * 4) || !w.r_next.grow(slots * 4) || !w.r_cnt.grow(8) ||
+      !w.r_gcol.grow(gmax * rlc_ncols(n) * 32) || !w.r_gfix.grow(gmax * rlc_ncols(n) * 96))
     return FTS_API_ENOMEM;
   uint8_t* hs = L.stage_buf((sel_big.size() + sel_small.size()) * 4);
   if (!hs) return FTS_API_ENOMEM;
@@ -1385,7 +1238,7 @@ static int rp_group_fallback(fts_ctx* c, Lane& L, const RpBatchDev& d, const Rlc
     gp.sel = sel;
     gp.sel_pts = npts;
     if (int rc = msm_prepare_plan(L, gp, gs == RP_GT2 ? MSM_SLOT_GT_SMALL : MSM_SLOT_GT_BIG)) return rc;
-    launch_rlc_group_test(d, r, c->d_tables, gp, sel, G, gs, w.r_gcol.as<uint32_t>(), w.r_gfix.as<uint32_t>(), nxt,
+    launch_rlc_group_test(d, r, c->d_tables.as<uint32_t>(), gp, sel, G, gs, w.r_gcol.as<uint32_t>(), w.r_gfix.as<uint32_t>(), nxt,
                           cnt, L.s, &L.tl);
     HIP_OK(hipGetLastError());
     return FTS_API_OK;
@@ -1419,7 +1272,7 @@ static int rp_group_fallback(fts_ctx* c, Lane& L, const RpBatchDev& d, const Rlc
   // left many proofs in large groups (the per-proof check's latency is one GLV
   // chain whatever their number, its work grows with it)
   if (sel_big.empty() || nfail <= RP_GT2_MIN) {
-    launch_rp_fallback(d, c->d_tables, nxt, nfail, L.s, &L.tl);
+    launch_rp_fallback(d, c->d_tables.as<uint32_t>(), nxt, nfail, L.s, &L.tl);
     HIP_OK(hipGetLastError());
     return FTS_API_OK;
   }
@@ -1434,7 +1287,7 @@ static int rp_group_fallback(fts_ctx* c, Lane& L, const RpBatchDev& d, const Rlc
   HIP_OK(L.sync());
   const int nfail2 = L.pin->flag;
   if (nfail2 == 0) return FTS_API_OK;
-  launch_rp_fallback(d, c->d_tables, nxt, nfail2, L.s, &L.tl);
+  launch_rp_fallback(d, c->d_tables.as<uint32_t>(), nxt, nfail2, L.s, &L.tl);
   HIP_OK(hipGetLastError());
   return FTS_API_OK;
 }
@@ -1482,9 +1335,9 @@ static int rp_enqueue(fts_ctx* c, Lane& L, int B, uint8_t* d_raw, uint32_t* d_sc
     mp.local_sort = c->msm_sort != 0;
     Workspace& w0 = L.ws;
     const size_t NC = rlc_ncols(n);
-    if (w0.r_msel.ensure((size_t)G * gs * 4) || w0.r_mcol.ensure((size_t)G * NC * 32) ||
-        w0.r_mfix.ensure((size_t)G * NC * 96) || w0.r_mqfix.ensure((size_t)G * NC * 96) ||
-        w0.r_mflag.ensure((size_t)G * 4))
+    if (!w0.r_msel.grow((size_t)G * gs * 4) || !w0.r_mcol.grow((size_t)G * NC * 32) ||
+        !w0.r_mfix.grow((size_t)G * NC * 96) || !w0.r_mqfix.grow((size_t)G * NC * 96) ||
+        !w0.r_mflag.grow((size_t)G * 4))
       return FTS_API_ENOMEM;
     int32_t* hs = L.sel_buf((size_t)G * gs);
     if (!hs) return FTS_API_ENOMEM;
@@ -1557,11 +1410,11 @@ static int rp_enqueue(fts_ctx* c, Lane& L, int B, uint8_t* d_raw, uint32_t* d_sc
     // one critical section, so the chain of events follows the enqueue order
     std::lock_guard<std::mutex> g(c->fx_mu);
     d.fx_wait = c->fx_last;
-    launch_rp_batch(d, r, c->d_tables, c->d_wtables, c->d_x0const, c->d_x0tmpl, L.s, L.s2, L.s3, L.s4, &L.tl,
+    launch_rp_batch(d, r, c->d_tables.as<uint32_t>(), c->d_wtables.as<uint32_t>(), c->d_x0const.as<uint8_t>(), c->d_x0tmpl.as<uint8_t>(), L.s, L.s2, L.s3, L.s4, &L.tl,
                     c->wbits);
     c->fx_last = d.ev_fx;
   } else {
-    launch_rp_batch(d, r, c->d_tables, c->d_wtables, c->d_x0const, c->d_x0tmpl, L.s, L.s2, L.s3, L.s4, &L.tl,
+    launch_rp_batch(d, r, c->d_tables.as<uint32_t>(), c->d_wtables.as<uint32_t>(), c->d_x0const.as<uint8_t>(), c->d_x0tmpl.as<uint8_t>(), L.s, L.s2, L.s3, L.s4, &L.tl,
                     c->wbits);
   }
   between();
@@ -1584,17 +1437,17 @@ static int rp_enqueue(fts_ctx* c, Lane& L, int B, uint8_t* d_raw, uint32_t* d_sc
 static int rp_locate_single(fts_ctx* c, Lane& L, RpPass& P) {
   const int B = P.d.B;
   Workspace& w = L.ws;
-  if (w.r_loc.ensure(4) || w.r_save.ensure(96)) return FTS_API_ENOMEM;
+  if (!w.r_loc.grow(4) || !w.r_save.grow(96)) return FTS_API_ENOMEM;
   L.tl.fallback();
   int32_t* loc = w.r_loc.as<int32_t>();
   HIP_OK(hipMemsetAsync(loc, 0xff, 4, L.s));
-  launch_rlc_locate(P.d, P.r, c->d_tables, w.r_save.as<uint32_t>(), loc, L.s, &L.tl);
+  launch_rlc_locate(P.d, P.r, c->d_tables.as<uint32_t>(), w.r_save.as<uint32_t>(), loc, L.s, &L.tl);
   HIP_OK(hipGetLastError());
   HIP_OK(hipMemcpyAsync(&L.pin->flag, loc, 4, hipMemcpyDeviceToHost, L.s));
   HIP_OK(L.sync());
   const int i = L.pin->flag;
   if (i < 0 || i >= B) return 0;
-  launch_rp_fallback(P.d, c->d_tables, loc, 1, L.s, &L.tl);
+  launch_rp_fallback(P.d, c->d_tables.as<uint32_t>(), loc, 1, L.s, &L.tl);
   HIP_OK(hipGetLastError());
   HIP_OK(hipMemcpyAsync(&L.pin->flag, P.d.status + i, 4, hipMemcpyDeviceToHost, L.s));
   HIP_OK(L.sync());
@@ -1712,8 +1565,8 @@ static void run_rp_groups(fts_ctx* c, const std::vector<Lane*>& lanes, const std
       RpGather g{};
       if (B > 0) {
         const size_t Bal = std::max(B, std::min(c->coalesce_max, (size_t)1 << 20));  // sized once for the largest pass
-        if (w.rp_raw.ensure(Bal * npts * 64) || w.rp_sc.ensure(Bal * RP_NSC * 32) || w.rp_status.ensure(Bal * 4) ||
-            w.rp_ipa.ensure(Bal * 4))
+        if (!w.rp_raw.grow(Bal * npts * 64) || !w.rp_sc.grow(Bal * RP_NSC * 32) || !w.rp_status.grow(Bal * 4) ||
+            !w.rp_ipa.grow(Bal * 4))
           return FTS_API_ENOMEM;
         g.G = (int)rpq[j].size();
         size_t off = 0;
@@ -1914,7 +1767,7 @@ int fts_rp_batch_stage(fts_ctx* c, size_t n, const uint8_t* const* rp_der, const
                        fts_rp_batch** out) {
   if (!c || !out || (n && (!rp_der || !rp_len || !com64))) return FTS_API_EINVAL;
   if (!c->shards.empty()) {  // one child batch per device, contiguous shards
-    fts_rp_batch* b = new fts_rp_batch();
+    std::unique_ptr<fts_rp_batch> b(new fts_rp_batch());
     b->B = (int)n;
     b->device = c->device;
     b->bounds = plan(n, nullptr, (int)c->shards.size());
@@ -1923,35 +1776,34 @@ int fts_rp_batch_stage(fts_ctx* c, size_t n, const uint8_t* const* rp_der, const
     int rc = run_shards(b->bounds, [&](int j, size_t lo, size_t hi) {
       return fts_rp_batch_stage(c->shards[j], hi - lo, rp_der + lo, rp_len + lo, com64 + 64 * lo, &b->parts[j]);
     });
-    if (rc != FTS_API_OK) {
-      fts_rp_batch_free(b);
-      return rc;
-    }
-    *out = b;
+    if (rc != FTS_API_OK) return rc;
+    *out = b.release();
     return FTS_API_OK;
   }
   if (c->device < 0) return FTS_API_EDEVICE;
   HIP_OK(hipSetDevice(c->device));
   RpHost h;
   parse_rp_batch(c->k, n, rp_der, rp_len, com64, h);
-  fts_rp_batch* b = new fts_rp_batch();
+  std::unique_ptr<fts_rp_batch> b(new fts_rp_batch());  // every early return releases it
   b->B = (int)n;
   b->device = c->device;
   size_t nb = std::max<size_t>(n, 1);
-  if (hipMalloc(&b->raw, std::max<size_t>(h.raw.size(), 64)) != hipSuccess ||
-      hipMalloc(&b->sc, std::max<size_t>(h.sc.size() * 4, 32)) != hipSuccess ||
-      hipMalloc(&b->status0, nb * 4) != hipSuccess || hipMalloc(&b->status, nb * 4) != hipSuccess ||
-      hipMalloc(&b->ipa_flag, nb * 4) != hipSuccess) {
-    fts_rp_batch_free(b);
+  if (!b->raw_mem.reserve(std::max<size_t>(h.raw.size(), 64)) ||
+      !b->sc_mem.reserve(std::max<size_t>(h.sc.size() * 4, 32)) || !b->status0_mem.reserve(nb * 4) ||
+      !b->status_mem.reserve(nb * 4) || !b->ipa_mem.reserve(nb * 4))
     return FTS_API_ENOMEM;
-  }
+  b->raw = b->raw_mem.as<uint8_t>();
+  b->sc = b->sc_mem.as<uint32_t>();
+  b->status0 = b->status0_mem.as<int32_t>();
+  b->status = b->status_mem.as<int32_t>();
+  b->ipa_flag = b->ipa_mem.as<int32_t>();
   if (n) {
     HIP_OK(hipMemcpy(b->raw, h.raw.data(), h.raw.size(), hipMemcpyHostToDevice));
     HIP_OK(hipMemcpy(b->sc, h.sc.data(), h.sc.size() * 4, hipMemcpyHostToDevice));
     HIP_OK(hipMemcpy(b->status0, h.status.data(), n * 4, hipMemcpyHostToDevice));
     HIP_OK(hipMemcpy(b->ipa_flag, h.ipa.data(), n * 4, hipMemcpyHostToDevice));
   }
-  *out = b;
+  *out = b.release();
   return FTS_API_OK;
 }
 
@@ -2031,7 +1883,7 @@ static int rp_dispatch(fts_ctx* c, RpReq& me) {
       me.cv.wait(lk);
       continue;
     }
-    Lane* L = c->lanes[c->free_lanes.back()];
+    Lane* L = c->lanes[c->free_lanes.back()].get();
     c->free_lanes.pop_back();
     L->alone = c->free_lanes.size() + 1 == c->lanes.size();
     // an idle device's first pass stops at gather_target proofs (the rest of the
@@ -2135,9 +1987,16 @@ int fts_ctx_reserve(fts_ctx* c, size_t max_pass_proofs) {
 struct fts_msm_batch {
   int N = 0;
   int device = 0;
+  DevBuf pts_mem, sc_mem, out_mem;
   uint32_t* pts = nullptr;  // [N][16] affine Montgomery
   uint32_t* sc = nullptr;   // [N][8] canonical scalars
   uint8_t* out = nullptr;   // 64-byte result
+  bool alloc(size_t n) {
+    if (!pts_mem.reserve(n * 64) || !sc_mem.reserve(n * 32) || !out_mem.reserve(64)) return false;
+    pts = pts_mem.as<uint32_t>(), sc = sc_mem.as<uint32_t>(), out = out_mem.as<uint8_t>();
+    return true;
+  }
+  ~fts_msm_batch() { hipSetDevice(device); }
   int ntim = 0;
   const char* tim_name[Timeline::CAP];
   float tim_ms[Timeline::CAP];
@@ -2145,52 +2004,29 @@ struct fts_msm_batch {
 };
 extern "C" {
 
-void fts_msm_free(fts_msm_batch* b) {
-  if (!b) return;
-  hipSetDevice(b->device);
-  for (void* p : {(void*)b->pts, (void*)b->sc, (void*)b->out})
-    if (p) hipFree(p);
-  delete b;
-}
+void fts_msm_free(fts_msm_batch* b) { delete b; }
 
 int fts_msm_stage(fts_ctx* c, size_t n, const uint8_t* points64, const uint8_t* scalars32, fts_msm_batch** out) {
   if (c && !c->shards.empty()) return fts_msm_stage(c->shards[0], n, points64, scalars32, out);
   if (!c || !out || !n || !points64 || !scalars32 || n > (size_t)(1u << 26)) return FTS_API_EINVAL;
   if (c->device < 0) return FTS_API_EDEVICE;
   HIP_OK(hipSetDevice(c->device));
-  fts_msm_batch* b = new fts_msm_batch();
+  std::unique_ptr<fts_msm_batch> b(new fts_msm_batch());
   b->N = (int)n;
   b->device = c->device;
-  uint8_t *rp = nullptr, *rs = nullptr;
-  uint32_t* bad = nullptr;
-  if (hipMalloc(&b->pts, n * 64) != hipSuccess || hipMalloc(&b->sc, n * 32) != hipSuccess ||
-      hipMalloc(&b->out, 64) != hipSuccess || hipMalloc(&rp, n * 64) != hipSuccess || hipMalloc(&rs, n * 32) != hipSuccess ||
-      hipMalloc(&bad, 4) != hipSuccess) {
-    for (void* p : {(void*)rp, (void*)rs, (void*)bad})
-      if (p) hipFree(p);
-    fts_msm_free(b);
-    return FTS_API_ENOMEM;
-  }
+  DevBuf rp, rs, bad;  // the raw inputs, released (with the null stream drained) on every exit
+  if (!b->alloc(n) || !rp.reserve(n * 64) || !rs.reserve(n * 32) || !bad.reserve(4)) return FTS_API_ENOMEM;
   uint32_t nbad = 0;
-  hipError_t e = hipMemcpy(rp, points64, n * 64, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(rs, scalars32, n * 32, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemset(bad, 0, 4);
+  hipError_t e = hipMemcpy(rp.p, points64, n * 64, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(rs.p, scalars32, n * 32, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemset(bad.p, 0, 4);
   if (e == hipSuccess) {
-    launch_msm_load((int)n, rp, rs, b->pts, b->sc, bad, 0);
-    e = hipMemcpy(&nbad, bad, 4, hipMemcpyDeviceToHost);
+    launch_msm_load((int)n, rp.as<uint8_t>(), rs.as<uint8_t>(), b->pts, b->sc, bad.as<uint32_t>(), 0);
+    e = hipMemcpy(&nbad, bad.p, 4, hipMemcpyDeviceToHost);
   }
-  hipFree(rp);
-  hipFree(rs);
-  hipFree(bad);
-  if (e != hipSuccess) {
-    fts_msm_free(b);
-    return FTS_API_EDEVICE;
-  }
-  if (nbad) {  // a point failed NewG1FromBytes (flags, range, on-curve)
-    fts_msm_free(b);
-    return FTS_API_EINVAL;
-  }
-  *out = b;
+  if (e != hipSuccess) return FTS_API_EDEVICE;
+  if (nbad) return FTS_API_EINVAL;  // a point failed NewG1FromBytes (flags, range, on-curve)
+  *out = b.release();
   return FTS_API_OK;
 }
 
@@ -2199,14 +2035,10 @@ int fts_msm_stage_multiples(fts_ctx* c, size_t n, const uint8_t* k32, const uint
   if (!c || !out || !n || !k32 || !scalars32 || n > (size_t)(1u << 26)) return FTS_API_EINVAL;
   if (c->device < 0) return FTS_API_EDEVICE;
   HIP_OK(hipSetDevice(c->device));
-  fts_msm_batch* b = new fts_msm_batch();
+  std::unique_ptr<fts_msm_batch> b(new fts_msm_batch());
   b->N = (int)n;
   b->device = c->device;
-  if (hipMalloc(&b->pts, n * 64) != hipSuccess || hipMalloc(&b->sc, n * 32) != hipSuccess ||
-      hipMalloc(&b->out, 64) != hipSuccess) {
-    fts_msm_free(b);
-    return FTS_API_ENOMEM;
-  }
+  if (!b->alloc(n)) return FTS_API_ENOMEM;
   // the temporaries on a private stream with stream-ordered allocation, synchronised
   // alone: a device-wide sync (hipDeviceSynchronize, or hipFree) here would stall
   // every lane's in-flight pass on a shared context
@@ -2221,7 +2053,7 @@ int fts_msm_stage_multiples(fts_ctx* c, size_t n, const uint8_t* k32, const uint
   if (e == hipSuccess) e = hipMemcpyAsync(rs, scalars32, n * 32, hipMemcpyHostToDevice, st);
   if (e == hipSuccess) {
     // B = the PP's ped[1] (table slot tb_G): a generator of G1
-    launch_msm_gen_points((int)n, rk, rs, c->d_tables + (size_t)tb_G(c->n) * fb_words_per_base(), jac, b->pts, b->sc,
+    launch_msm_gen_points((int)n, rk, rs, c->d_tables.as<uint32_t>() + (size_t)tb_G(c->n) * fb_words_per_base(), jac, b->pts, b->sc,
                           st);
     e = hipGetLastError();
   }
@@ -2232,11 +2064,8 @@ int fts_msm_stage_multiples(fts_ctx* c, size_t n, const uint8_t* k32, const uint
     if (e == hipSuccess) e = e2;
     hipStreamDestroy(st);
   }
-  if (e != hipSuccess) {
-    fts_msm_free(b);
-    return e == hipErrorOutOfMemory ? FTS_API_ENOMEM : FTS_API_EDEVICE;
-  }
-  *out = b;
+  if (e != hipSuccess) return e == hipErrorOutOfMemory ? FTS_API_ENOMEM : FTS_API_EDEVICE;
+  *out = b.release();
   return FTS_API_OK;
 }
 
@@ -2336,18 +2165,7 @@ int fts_msm_g1(fts_ctx* c, size_t n, const uint8_t* points64, const uint8_t* sca
   return rc;
 }
 
-void fts_rp_batch_free(fts_rp_batch* b) {
-  if (!b) return;
-  if (!b->parts.empty() || !b->part_ctx.empty()) {
-    for (fts_rp_batch* q : b->parts) fts_rp_batch_free(q);
-    delete b;
-    return;
-  }
-  hipSetDevice(b->device);
-  for (void* p : {(void*)b->raw, (void*)b->sc, (void*)b->status0, (void*)b->status, (void*)b->ipa_flag})
-    if (p) hipFree(p);
-  delete b;
-}
+void fts_rp_batch_free(fts_rp_batch* b) { delete b; }
 
 // a staging slot sized for n proofs (idle one reused, else a new one); nullptr on
 // allocation failure
@@ -2361,39 +2179,15 @@ static RpSlot* slot_acquire(fts_ctx* c, size_t n) {
     }
   }
   if (!sl) {
-    sl = new RpSlot();
-    sl->b = new fts_rp_batch();
-    sl->b->device = c->device;
-    if (hipStreamCreateWithFlags(&sl->s, hipStreamNonBlocking) != hipSuccess ||
-        hipEventCreateWithFlags(&sl->done, hipEventBlockingSync | hipEventDisableTiming) != hipSuccess) {
-      if (sl->s) hipStreamDestroy(sl->s);
-      delete sl->b;
-      delete sl;
-      return nullptr;
-    }
+    std::unique_ptr<RpSlot> fresh(new RpSlot());
+    if (!fresh->create(c->device)) return nullptr;
+    sl = fresh.get();
     std::lock_guard<std::mutex> g(c->slot_mu);
-    c->slots.push_back(sl);
+    c->slots.push_back(std::move(fresh));
   }
   const size_t npts = (size_t)rp_npts(c->k);
   const size_t in_bytes = n * (npts * 64 + RP_NSC * 32 + 8), dev_bytes = in_bytes + n * 4;
-  bool ok = true;
-  if (in_bytes > sl->pin_cap) {
-    if (sl->pin) (void)hipHostFree(sl->pin);
-    sl->pin = nullptr;
-    const size_t want = std::max(in_bytes, sl->pin_cap + sl->pin_cap / 2);
-    sl->pin_cap = 0;
-    if (hipHostMalloc((void**)&sl->pin, want, 0) == hipSuccess) sl->pin_cap = want;
-    else ok = false;
-  }
-  if (ok && dev_bytes > sl->dev_cap) {
-    if (sl->dev) hipFree(sl->dev);
-    sl->dev = nullptr;
-    const size_t want = std::max(dev_bytes, sl->dev_cap + sl->dev_cap / 2);
-    sl->dev_cap = 0;
-    if (hipMalloc((void**)&sl->dev, want) == hipSuccess) sl->dev_cap = want;
-    else ok = false;
-  }
-  if (!ok) {
+  if (!sl->size(in_bytes, dev_bytes)) {
     std::lock_guard<std::mutex> g(c->slot_mu);
     c->free_slots.push_back(sl);
     return nullptr;
@@ -2420,10 +2214,11 @@ int fts_rp_verify_batch(fts_ctx* c, size_t n, const uint8_t* const* rp_der, cons
   if (!sl) return not_run(FTS_API_ENOMEM);
   const size_t npts = (size_t)rp_npts(c->k);
   const size_t raw_b = n * npts * 64, sc_b = n * RP_NSC * 32, st_b = n * 4;
-  uint8_t* p = sl->pin;
+  uint8_t* p = sl->pin.as<uint8_t>();
+  uint8_t* const dev = sl->dev.as<uint8_t>();
   parse_rp_into(c->k, n, rp_der, rp_len, com64, p, reinterpret_cast<uint32_t*>(p + raw_b),
                 reinterpret_cast<int32_t*>(p + raw_b + sc_b), reinterpret_cast<int32_t*>(p + raw_b + sc_b + st_b));
-  fts_rp_batch* b = sl->b;
+  fts_rp_batch* b = sl->b.get();
   // the slot's batch object serves unrelated callers in turn: the adaptive
   // group-test state (FTS_GT_ADAPT) is per caller batch, so an honest call never
   // inherits the dense schedule of the previous caller's tampered one
@@ -2432,13 +2227,13 @@ int fts_rp_verify_batch(fts_ctx* c, size_t n, const uint8_t* const* rp_der, cons
   b->merged = 1;
   b->ntim = 0;
   b->B = (int)n;
-  b->raw = sl->dev;
-  b->sc = reinterpret_cast<uint32_t*>(sl->dev + raw_b);
-  b->status0 = reinterpret_cast<int32_t*>(sl->dev + raw_b + sc_b);
-  b->ipa_flag = reinterpret_cast<int32_t*>(sl->dev + raw_b + sc_b + st_b);
-  b->status = reinterpret_cast<int32_t*>(sl->dev + raw_b + sc_b + 2 * st_b);
+  b->raw = dev;
+  b->sc = reinterpret_cast<uint32_t*>(dev + raw_b);
+  b->status0 = reinterpret_cast<int32_t*>(dev + raw_b + sc_b);
+  b->ipa_flag = reinterpret_cast<int32_t*>(dev + raw_b + sc_b + st_b);
+  b->status = reinterpret_cast<int32_t*>(dev + raw_b + sc_b + 2 * st_b);
   int rc = FTS_API_OK;
-  if (hipMemcpyAsync(sl->dev, sl->pin, raw_b + sc_b + 2 * st_b, hipMemcpyHostToDevice, sl->s) != hipSuccess ||
+  if (hipMemcpyAsync(dev, p, raw_b + sc_b + 2 * st_b, hipMemcpyHostToDevice, sl->s) != hipSuccess ||
       hipEventRecord(sl->done, sl->s) != hipSuccess || hipEventSynchronize(sl->done) != hipSuccess)
     rc = FTS_API_EDEVICE;
   if (rc == FTS_API_OK) rc = fts_rp_batch_verify(c, b, status);
@@ -2468,51 +2263,18 @@ static ActSlot* aslot_acquire(fts_ctx* c) {
       return sl;
     }
   }
-  ActSlot* sl = new ActSlot();
-  sl->b = new fts_rp_batch();
-  sl->b->device = c->device;
-  if (hipStreamCreateWithFlags(&sl->s, hipStreamNonBlocking) != hipSuccess ||
-      hipEventCreateWithFlags(&sl->done, hipEventBlockingSync | hipEventDisableTiming) != hipSuccess ||
-      hipEventCreate(&sl->ev_sig[0]) != hipSuccess || hipEventCreate(&sl->ev_sig[1]) != hipSuccess ||
-      hipEventCreate(&sl->ev_sig[2]) != hipSuccess) {
-    for (hipEvent_t e : sl->ev_sig)
-      if (e) hipEventDestroy(e);
-    if (sl->done) hipEventDestroy(sl->done);
-    if (sl->s) hipStreamDestroy(sl->s);
-    delete sl->b;
-    delete sl;
-    return nullptr;
-  }
+  std::unique_ptr<ActSlot> sl(new ActSlot());
+  bool ok = sl->create(c->device);
+  for (Event& e : sl->ev_sig) ok = ok && e.create() == hipSuccess;
+  if (!ok) return nullptr;
   std::lock_guard<std::mutex> g(c->slot_mu);
-  c->aslots.push_back(sl);
-  return sl;
+  c->aslots.push_back(std::move(sl));
+  return c->aslots.back().get();
 }
 
 static void aslot_release(fts_ctx* c, ActSlot* sl) {
   std::lock_guard<std::mutex> g(c->slot_mu);
   c->free_aslots.push_back(sl);
-}
-
-// grow the slot's pinned and device buffers geometrically (hipFree synchronises the
-// whole device: a slot must not be re-allocated on every slightly larger call)
-static bool aslot_size(ActSlot* sl, size_t pin_bytes, size_t dev_bytes) {
-  if (pin_bytes > sl->pin_cap) {
-    if (sl->pin) (void)hipHostFree(sl->pin);
-    sl->pin = nullptr;
-    const size_t want = std::max(pin_bytes, sl->pin_cap + sl->pin_cap / 2);
-    sl->pin_cap = 0;
-    if (hipHostMalloc((void**)&sl->pin, want, 0) != hipSuccess) return false;
-    sl->pin_cap = want;
-  }
-  if (dev_bytes > sl->dev_cap) {
-    if (sl->dev) hipFree(sl->dev);
-    sl->dev = nullptr;
-    const size_t want = std::max(dev_bytes, sl->dev_cap + sl->dev_cap / 2);
-    sl->dev_cap = 0;
-    if (hipMalloc((void**)&sl->dev, want) != hipSuccess) return false;
-    sl->dev_cap = want;
-  }
-  return true;
 }
 
 // Parse an action call into slot sl: sigma batch + range-proof records in their
@@ -2614,8 +2376,8 @@ static int act_stage(fts_ctx* c, ActSlot* sl, const std::vector<ActionIn>& acts)
     sl->host_buf.resize(std::max<size_t>(pin_end, 256));
     hp = sl->host_buf.data();
   } else {
-    if (!aslot_size(sl, std::max<size_t>(pin_end, 256), std::max<size_t>(dev_end, 256))) return FTS_API_ENOMEM;
-    hp = sl->pin;
+    if (!sl->size(std::max<size_t>(pin_end, 256), std::max<size_t>(dev_end, 256))) return FTS_API_ENOMEM;
+    hp = sl->pin.as<uint8_t>();
   }
   SigAction* hact = reinterpret_cast<SigAction*>(hp + o_act);
   int32_t* hsst = reinterpret_cast<int32_t*>(hp + o_sst);
@@ -2776,8 +2538,8 @@ static int act_stage(fts_ctx* c, ActSlot* sl, const std::vector<ActionIn>& acts)
   sl->phase_ms[1] = (float)(t_p2 - t_p1);
   sl->phase_ms[2] = (float)(t1 - t_p2);
   // the slot's views: range-proof batch and sigma batch over the device copy
-  uint8_t* dv = sl->dev;
-  fts_rp_batch* b = sl->b;
+  uint8_t* dv = sl->dev.as<uint8_t>();
+  fts_rp_batch* b = sl->b.get();
   b->B = rp_total;
   b->raw = dv + o_rraw;
   b->sc = reinterpret_cast<uint32_t*>(dv + o_rsc);
@@ -2822,7 +2584,7 @@ static int act_stage(fts_ctx* c, ActSlot* sl, const std::vector<ActionIn>& acts)
     HIP_OK(hipEventRecord(sl->ev_sig[0], sl->s));
     if (SA) launch_sig_prep(sd, sl->s);
     HIP_OK(hipEventRecord(sl->ev_sig[1], sl->s));
-    if (SA) launch_sig_finish(sd, c->d_tables, c->n, sl->s);
+    if (SA) launch_sig_finish(sd, c->d_tables.as<uint32_t>(), c->n, sl->s);
     HIP_OK(hipEventRecord(sl->ev_sig[2], sl->s));
     HIP_OK(hipGetLastError());
   }
@@ -2838,7 +2600,7 @@ static int act_verify(fts_ctx* c, const std::vector<ActionIn>& acts, int32_t* st
   if (!sl) return FTS_API_ENOMEM;
   int rc = act_stage(c, sl, acts);
   if (rc == FTS_API_OK && sl->b->B) {
-    RpReq me(sl->b, sl->rp_res.data(), sl);
+    RpReq me(sl->b.get(), sl->rp_res.data(), sl);
     rc = rp_dispatch(c, me);
     c->act_locate_skip.store(sl->b->locate_skip, std::memory_order_relaxed);
     c->act_locate_backoff.store(sl->b->locate_backoff, std::memory_order_relaxed);
@@ -2881,6 +2643,10 @@ static int act_verify(fts_ctx* c, const std::vector<ActionIn>& acts, int32_t* st
       if (fail_index) fail_index[i] = idx;
     }
   }
+  // an error path may leave the upload or the sigma kernels queued on the slot's
+  // stream, still reading its pinned / device buffers: drain it before the next
+  // caller may reuse (or re-allocate) them
+  if (rc != FTS_API_OK && sl->s) (void)hipStreamSynchronize(sl->s);
   aslot_release(c, sl);
   return rc;
 }
@@ -2897,9 +2663,8 @@ extern "C" int fts_debug_stage_actions(fts_ctx* c, size_t n_tr, const fts_transf
   for (size_t i = 0; i < n_is; i++)
     acts.push_back(ActionIn{SIG_ST, nullptr, 0, issues[i].tokens, issues[i].n_tok,
                             der::Span{issues[i].proof, issues[i].proof ? issues[i].proof_len : 0}});
-  ActSlot sl;
-  fts_rp_batch b;
-  sl.b = &b;
+  ActSlot sl;  // host-only: no stream, no device buffer
+  sl.b.reset(new fts_rp_batch());
   double tot[4] = {0, 0, 0, 0};
   if (int rc = act_stage(c, &sl, acts)) return rc;  // untimed: the slot's buffers grow (page faults) once
   for (int r = 0; r < reps; r++) {
@@ -2907,7 +2672,6 @@ extern "C" int fts_debug_stage_actions(fts_ctx* c, size_t n_tr, const fts_transf
     tot[0] += sl.parse_ms;
     for (int q = 0; q < 3; q++) tot[1 + q] += sl.phase_ms[q];
   }
-  sl.b = nullptr;
   if (ms_avg)
     for (int q = 0; q < 4; q++) ms_avg[q] = (float)(tot[q] / reps);
   return FTS_API_OK;
@@ -3268,7 +3032,7 @@ int fts_token_open_batch(fts_ctx* c, size_t n, const fts_token_opening* items, i
   Lane& L = *lg.L;
   const double t0 = now_ms();
   uint8_t* st = L.stage_buf(n * OPEN_REC);
-  if (!st || L.ws.open_rec.ensure(n * OPEN_REC)) return FTS_API_ENOMEM;
+  if (!st || !L.ws.open_rec.grow(n * OPEN_REC)) return FTS_API_ENOMEM;
   uint8_t* h_raw = st;
   uint32_t* h_sc = reinterpret_cast<uint32_t*>(st + n * 64);
   int32_t* h_st = reinterpret_cast<int32_t*>(st + n * 160);
@@ -3309,7 +3073,7 @@ int fts_token_open_batch(fts_ctx* c, size_t n, const fts_token_opening* items, i
   L.tl.begin(L.s);
   HIP_OK(hipMemcpyAsync(d, st, n * OPEN_REC, hipMemcpyHostToDevice, L.s));
   L.tl.mark("h2d_open", L.s, 0);
-  launch_open_check((int)n, d, reinterpret_cast<const uint32_t*>(d + n * 64), c->d_tables, c->n,
+  launch_open_check((int)n, d, reinterpret_cast<const uint32_t*>(d + n * 64), c->d_tables.as<uint32_t>(), c->n,
                     reinterpret_cast<int32_t*>(d + n * 160), L.s);
   L.tl.mark("k_open_check", L.s, OPEN_PRODUCTS * (double)n);
   HIP_OK(hipGetLastError());
@@ -3416,7 +3180,7 @@ static int rp_prove_device(fts_ctx* c, Lane& L, size_t N, const PvInput& input, 
                o_ch = ar.take<uint32_t>(B0 * rp_nch(k) * 8), o_sc = ar.take<uint32_t>(B0 * RP_NSC * 8),
                o_status = ar.take<int32_t>(B0), o_x0 = ar.take<uint8_t>(B0 * x0_var_bytes(n)),
                o_hs = ar.take<uint8_t>(B0 * PV_HSLOT);
-  if (L.ws.pv.ensure(ar.off)) return FTS_API_ENOMEM;
+  if (!L.ws.pv.grow(ar.off)) return FTS_API_ENOMEM;
   uint8_t* base = L.ws.pv.as<uint8_t>();
   // pinned staging: inputs [values | rnd | bf], outputs [points | scalars]
   const size_t in_bytes = B0 * (8 + pv_nrnd(n) * 32 + 32), out_pts_b = B0 * pv_npts(k) * 64,
@@ -3449,7 +3213,7 @@ static int rp_prove_device(fts_ctx* c, Lane& L, size_t N, const PvInput& input, 
     HIP_OK(hipMemcpyAsync(base + o_bf, h_bf, B * 32, hipMemcpyHostToDevice, L.s));
     PvDev d;
     d.B = (int)B, d.n = n, d.k = k;
-    d.tables = c->d_tables;
+    d.tables = c->d_tables.as<uint32_t>();
     d.values = reinterpret_cast<const uint64_t*>(base + o_val);
     d.rnd = reinterpret_cast<const uint32_t*>(base + o_rnd);
     d.bf = reinterpret_cast<const uint32_t*>(base + o_bf);
@@ -3468,7 +3232,7 @@ static int rp_prove_device(fts_ctx* c, Lane& L, size_t N, const PvInput& input, 
     d.hslot = base + o_hs;
     const double h1 = now_ms();
     L.tl.begin(L.s);
-    launch_rp_prove(d, stages, c->d_x0const, c->d_x0tmpl, L.s, &L.tl);
+    launch_rp_prove(d, stages, c->d_x0const.as<uint8_t>(), c->d_x0tmpl.as<uint8_t>(), L.s, &L.tl);
     HIP_OK(hipGetLastError());
     uint8_t* h_pts = stg + in_bytes;
     uint32_t* h_fr = reinterpret_cast<uint32_t*>(stg + in_bytes + out_pts_b);
@@ -3637,14 +3401,14 @@ static int actions_prove_device(fts_ctx* c, size_t A, const fts_action_witness* 
   const size_t o_act = ar.take<SpAction>(A), o_sc = ar.take<uint32_t>(nsc * 8), o_jac = ar.take<uint32_t>(npt * 24),
                o_aff = ar.take<uint32_t>(npt * 16), o_be = ar.take<uint8_t>(npt * 64), o_msg = ar.take<uint8_t>(nmsg),
                o_out = ar.take<uint32_t>(nout * 8);
-  if (L.ws.sp.ensure(ar.off)) return FTS_API_ENOMEM;
+  if (!L.ws.sp.grow(ar.off)) return FTS_API_ENOMEM;
   uint8_t* base = L.ws.sp.as<uint8_t>();
   std::vector<uint8_t> h_be(npt * 64);
   std::vector<uint32_t> h_out(nout * 8);
   HIP_OK(hipMemcpyAsync(base + o_act, act.data(), A * sizeof(SpAction), hipMemcpyHostToDevice, L.s));
   HIP_OK(hipMemcpyAsync(base + o_sc, h_sc.data(), nsc * 32, hipMemcpyHostToDevice, L.s));
   SpDev d;
-  d.A = (int)A, d.tables = c->d_tables, d.n = n;
+  d.A = (int)A, d.tables = c->d_tables.as<uint32_t>(), d.n = n;
   d.act = reinterpret_cast<const SpAction*>(base + o_act);
   d.sc = reinterpret_cast<const uint32_t*>(base + o_sc);
   d.jac = reinterpret_cast<uint32_t*>(base + o_jac);

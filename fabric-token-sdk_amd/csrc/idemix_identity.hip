@@ -30,8 +30,8 @@
 
 #include <algorithm>
 #include <atomic>
-#include <condition_variable>
 #include <functional>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <type_traits>
@@ -48,6 +48,7 @@
 #include "device/fp256bn.hpp"
 #include "device/pairing.hpp"
 #include "host/bn254_host.hpp"
+#include "host/hip_owned.hpp"
 #include "host/pb.hpp"
 
 namespace fts {
@@ -1306,12 +1307,10 @@ constexpr int NSLOT = 8;  // calls in flight per handle (each slot: its own stre
                           // 12 concurrent calls hit HSA_STATUS_ERROR_OUT_OF_RESOURCES dispatching the
                           // scratch-using pairing kernels, gpurun_out/ns)
 struct Slot {
-  hipStream_t stream = nullptr;
-  uint8_t* d_buf = nullptr;
-  size_t d_cap = 0;
-  uint8_t* h_buf = nullptr;
-  size_t h_cap = 0;
-  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+  Stream stream;
+  DevBuf d_buf;
+  PinBuf h_buf;
+  Event ev[3];
   float ms[2] = {0.f, 0.f};
   uint32_t stats[2] = {0u, 0u};
 };
@@ -1321,13 +1320,10 @@ struct Slot {
 struct fts_idemix_idv {
   int device = -1;
   int curve = 1;
-  uint32_t* d_tables = nullptr;  // HSk, HRand, HAttrs[0..3], g1
-  uint32_t* d_lines = nullptr;   // lines of W, then of g2
-  uint32_t* d_hash = nullptr;    // ipk.Hash as 8 big-endian words
-  std::mutex mu;
-  std::condition_variable cv;
-  idv::Slot slot[idv::NSLOT];
-  bool busy[idv::NSLOT] = {};
+  fts::DevBuf d_tables;  // HSk, HRand, HAttrs[0..3], g1
+  fts::DevBuf d_lines;   // lines of W, then of g2
+  fts::DevBuf d_hash;    // ipk.Hash as 8 big-endian words
+  fts::SlotRing<idv::Slot, idv::NSLOT> ring;  // its lock also guards last_* and g2_seen
   float last_ms[2] = {0.f, 0.f};
   // batch pairing check (k_idv_bp_*; FTS_IDV_BATCH=0 pairs every identity, the A/B
   // and pre-round-6 path); last call's groups and identities paired one by one
@@ -1337,23 +1333,12 @@ struct fts_idemix_idv {
   // verdict): an honest stream carries one key per epoch, and k_idv_g2_check is
   // one 254-step G2 chain on one lane (7.7 ms, on the call's critical path)
   std::unordered_map<std::string, int32_t> g2_seen;
+  ~fts_idemix_idv() {
+    if (device >= 0) (void)hipSetDevice(device);
+  }
 };
 
 namespace idv {
-void idv_free(fts_idemix_idv* k) {
-  if (!k) return;
-  if (k->device >= 0) (void)hipSetDevice(k->device);
-  for (auto& S : k->slot) {
-    if (S.stream) (void)hipStreamSynchronize(S.stream), (void)hipStreamDestroy(S.stream);
-    for (auto& e : S.ev)
-      if (e) (void)hipEventDestroy(e);
-    if (S.d_buf) (void)hipFree(S.d_buf);
-    if (S.h_buf) (void)hipHostFree(S.h_buf);
-  }
-  for (uint32_t* p : {k->d_tables, k->d_lines, k->d_hash})
-    if (p) (void)hipFree(p);
-  delete k;
-}
 int nlines(bool bn) { return bn ? pair::n_lines<pairc::Bn254>() : pair::n_lines<pairc::Fp256bn>(); }
 }  // namespace idv
 
@@ -1403,15 +1388,11 @@ int fts_idemix_idv_create(int device, const uint8_t* ipk, size_t ipk_len, int cu
   }
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return FTS_API_EDEVICE;
-  fts_idemix_idv* k = new fts_idemix_idv();
+  std::unique_ptr<fts_idemix_idv> k(new fts_idemix_idv());
   k->device = device;
   k->curve = curve_id;
   if (const char* e = getenv("FTS_IDV_BATCH")) k->batch = atoi(e) != 0;
-  auto fail = [&](int rc) {
-    idv_free(k);
-    return rc;
-  };
-  if (hipSetDevice(device) != hipSuccess) return fail(FTS_API_EDEVICE);
+  if (hipSetDevice(device) != hipSuccess) return FTS_API_EDEVICE;
   uint32_t hw[8] = {0};
   {
     uint8_t h[32] = {0};
@@ -1421,52 +1402,50 @@ int fts_idemix_idv_create(int device, const uint8_t* ipk, size_t ipk_len, int cu
   }
   const size_t wpb = bn ? fb_words_per_base() : fbn_words_per_base();
   const size_t nl = (size_t)nlines(bn) * pair::LINE_WORDS;
-  hipStream_t s0 = nullptr;
-  uint32_t *d_bases = nullptr, *d_scr = nullptr;
-  uint8_t* d_w = nullptr;
-  int32_t* d_ok = nullptr;
+  Stream s0;
+  DevBuf bases_buf, scr_buf, w_buf, ok_buf;
   const size_t scr_b = bn ? table_build_scratch_bytes(NB) : (size_t)NB * 16 * 4;
-  bool ok = hipStreamCreateWithFlags(&s0, hipStreamNonBlocking) == hipSuccess &&
-            hipMalloc(&k->d_tables, (size_t)NB * wpb * 4) == hipSuccess &&
-            hipMalloc(&k->d_lines, 2 * nl * 4) == hipSuccess && hipMalloc(&k->d_hash, 32) == hipSuccess &&
-            hipMalloc(&d_bases, sizeof bases) == hipSuccess && hipMalloc(&d_scr, scr_b) == hipSuccess &&
-            hipMalloc(&d_w, 128) == hipSuccess && hipMalloc(&d_ok, 64) == hipSuccess &&
-            hipMemcpyAsync(d_bases, bases, sizeof bases, hipMemcpyHostToDevice, s0) == hipSuccess &&
-            hipMemcpyAsync(d_w, wraw, 128, hipMemcpyHostToDevice, s0) == hipSuccess &&
-            hipMemcpyAsync(k->d_hash, hw, 32, hipMemcpyHostToDevice, s0) == hipSuccess &&
-            hipMemsetAsync(d_ok, 0, 64, s0) == hipSuccess;
+  bool ok = s0.create() == hipSuccess && k->d_tables.reserve((size_t)NB * wpb * 4) &&
+            k->d_lines.reserve(2 * nl * 4) && k->d_hash.reserve(32) && bases_buf.reserve(sizeof bases) &&
+            scr_buf.reserve(scr_b) && w_buf.reserve(128) && ok_buf.reserve(64);
+  uint32_t* const d_tables = k->d_tables.as<uint32_t>();
+  uint32_t* const d_lines = k->d_lines.as<uint32_t>();
+  uint32_t *const d_bases = bases_buf.as<uint32_t>(), *const d_scr = scr_buf.as<uint32_t>();
+  uint8_t* const d_w = w_buf.as<uint8_t>();
+  int32_t* const d_ok = ok_buf.as<int32_t>();
+  ok = ok && hipMemcpyAsync(d_bases, bases, sizeof bases, hipMemcpyHostToDevice, s0) == hipSuccess &&
+       hipMemcpyAsync(d_w, wraw, 128, hipMemcpyHostToDevice, s0) == hipSuccess &&
+       hipMemcpyAsync(k->d_hash.p, hw, 32, hipMemcpyHostToDevice, s0) == hipSuccess &&
+       hipMemsetAsync(d_ok, 0, 64, s0) == hipSuccess;
   int32_t hok[NB + 1] = {0};
   if (ok) {
     if (bn) {
-      launch_build_tables(d_bases, NB, k->d_tables, d_scr, s0);
-      launch_lines<BnCurve>(d_w, k->d_lines, d_ok + NB, s0);
+      launch_build_tables(d_bases, NB, d_tables, d_scr, s0);
+      launch_lines<BnCurve>(d_w, d_lines, d_ok + NB, s0);
     } else {
-      fbn_build_tables(d_bases, NB, d_scr, d_ok, k->d_tables, s0);
-      launch_lines<FbnCurve>(d_w, k->d_lines, d_ok + NB, s0);
+      fbn_build_tables(d_bases, NB, d_scr, d_ok, d_tables, s0);
+      launch_lines<FbnCurve>(d_w, d_lines, d_ok + NB, s0);
     }
     ok = hipGetLastError() == hipSuccess &&
          hipMemcpyAsync(hok, d_ok, sizeof hok, hipMemcpyDeviceToHost, s0) == hipSuccess &&
          hipStreamSynchronize(s0) == hipSuccess;
   }
-  if (s0) (void)hipStreamSynchronize(s0);
-  for (void* p : {(void*)d_bases, (void*)d_scr, (void*)d_w, (void*)d_ok})
-    if (p) (void)hipFree(p);
-  if (s0) (void)hipStreamDestroy(s0);
-  if (!ok) return fail(FTS_API_EDEVICE);
+  if (s0) (void)hipStreamSynchronize(s0);  // an error path may leave copies queued on s0
+  if (!ok) return FTS_API_EDEVICE;
   bool valid = hok[NB] == 1;  // W on the twist
   if (!bn)
     for (int b = 0; b < NB; b++) valid = valid && hok[b] == 1;
-  if (!valid) return fail(FTS_API_EPP);
-  for (auto& S : k->slot) {
-    ok = ok && hipStreamCreateWithFlags(&S.stream, hipStreamNonBlocking) == hipSuccess;
-    for (auto& e : S.ev) ok = ok && hipEventCreate(&e) == hipSuccess;
+  if (!valid) return FTS_API_EPP;
+  for (auto& S : k->ring.slot) {
+    ok = ok && S.stream.create() == hipSuccess;
+    for (auto& e : S.ev) ok = ok && e.create() == hipSuccess;
   }
-  if (!ok) return fail(FTS_API_EDEVICE);
-  *out = k;
+  if (!ok) return FTS_API_EDEVICE;
+  *out = k.release();
   return FTS_API_OK;
 }
 
-void fts_idemix_idv_destroy(fts_idemix_idv* k) { idv::idv_free(k); }
+void fts_idemix_idv_destroy(fts_idemix_idv* k) { delete k; }
 
 int fts_idemix_identity_verify_batch(fts_idemix_idv* K, size_t n, const uint8_t* const* ids, const size_t* id_len,
                                      int32_t* status) {
@@ -1474,31 +1453,11 @@ int fts_idemix_identity_verify_batch(fts_idemix_idv* K, size_t n, const uint8_t*
   if (!K || n > (size_t)(1u << 22) || (n && (!ids || !id_len || !status))) return FTS_API_EINVAL;
   if (n == 0) return FTS_API_OK;
   const bool bn = K->curve == FTS_CURVE_BN254;
-  int k = -1;
-  {
-    std::unique_lock<std::mutex> l(K->mu);
-    K->cv.wait(l, [&] {
-      for (int j = 0; j < NSLOT; j++)
-        if (!K->busy[j]) return true;
-      return false;
-    });
-    for (int j = 0; j < NSLOT && k < 0; j++)
-      if (!K->busy[j]) k = j;
-    K->busy[k] = true;
-  }
-  struct Guard {
-    fts_idemix_idv* K;
-    int k;
-    ~Guard() {
-      if (K->slot[k].stream) (void)hipStreamSynchronize(K->slot[k].stream);
-      std::lock_guard<std::mutex> l(K->mu);
-      K->last_ms[0] = K->slot[k].ms[0], K->last_ms[1] = K->slot[k].ms[1];
-      K->last_stats[0] = K->slot[k].stats[0], K->last_stats[1] = K->slot[k].stats[1];
-      K->busy[k] = false;
-      K->cv.notify_one();
-    }
-  } guard{K, k};
-  Slot& D = K->slot[k];
+  auto guard = K->ring.acquire([K](Slot& S) {
+    K->last_ms[0] = S.ms[0], K->last_ms[1] = S.ms[1];
+    K->last_stats[0] = S.stats[0], K->last_stats[1] = S.stats[1];
+  });
+  Slot& D = guard.slot();
   ICHK(hipSetDevice(K->device));
   // staged (host + device): rec | pts | epk | status | eidx | distinct epoch keys (BN254);
   // device only: zk | pin | scratch | msg | g2ok
@@ -1514,19 +1473,9 @@ int fts_idemix_identity_verify_batch(fts_idemix_idv* K, size_t n, const uint8_t*
   const size_t o_msg = (o_scr + scr_w * 4 + 255) & ~size_t(255);
   const size_t o_g2ok = (o_msg + (size_t)MSG_MAX * n + 255) & ~size_t(255);
   const size_t d_need = o_g2ok + 2 * n * 4;  // U verdicts, then the M key indices to check
-  if (D.h_cap < h_need) {
-    if (D.h_buf) (void)hipHostFree(D.h_buf);
-    D.h_buf = nullptr, D.h_cap = 0;
-    if (hipHostMalloc(&D.h_buf, h_need + h_need / 2, hipHostMallocDefault) != hipSuccess) return FTS_API_ENOMEM;
-    D.h_cap = h_need + h_need / 2;
-  }
-  if (D.d_cap < d_need) {
-    if (D.d_buf) (void)hipFree(D.d_buf);
-    D.d_buf = nullptr, D.d_cap = 0;
-    if (hipMalloc(&D.d_buf, d_need + d_need / 2) != hipSuccess) return FTS_API_ENOMEM;
-    D.d_cap = d_need + d_need / 2;
-  }
-  uint8_t* h = D.h_buf;
+  if (D.h_buf.cap < h_need && !D.h_buf.reserve(h_need + h_need / 2)) return FTS_API_ENOMEM;
+  if (D.d_buf.cap < d_need && !D.d_buf.reserve(d_need + d_need / 2)) return FTS_API_ENOMEM;
+  uint8_t* h = D.h_buf.as<uint8_t>();
   const uint32_t* rmod = bn ? kRbn : kRfbn;
   const size_t CH = 1024, nch = (n + CH - 1) / CH;
   host_parallel_for(nch, [&](size_t c) {
@@ -1580,7 +1529,7 @@ int fts_idemix_identity_verify_batch(fts_idemix_idv* K, size_t n, const uint8_t*
   int32_t* miss = reinterpret_cast<int32_t*>(h + o_miss);
   size_t M = 0;
   if (bn) {
-    std::lock_guard<std::mutex> l(K->mu);
+    std::lock_guard<std::mutex> l(K->ring.mu);
     for (size_t j = 0; j < U; j++) {
       const auto it = K->g2_seen.find(std::string(reinterpret_cast<const char*>(h + o_uk + 128 * j), 128));
       if (it != K->g2_seen.end()) {
@@ -1591,7 +1540,7 @@ int fts_idemix_identity_verify_batch(fts_idemix_idv* K, size_t n, const uint8_t*
       }
     }
   }
-  uint8_t* d = D.d_buf;
+  uint8_t* d = D.d_buf.as<uint8_t>();
   ICHK(hipMemcpyAsync(d, h, o_uk + U * 128, hipMemcpyHostToDevice, D.stream));
   ICHK(hipEventRecord(D.ev[0], D.stream));
   // batch pairing check: group sums, one pairing product per group, the identities
@@ -1604,7 +1553,7 @@ int fts_idemix_identity_verify_batch(fts_idemix_idv* K, size_t n, const uint8_t*
   c.zk = reinterpret_cast<int32_t*>(d + o_zk), c.st = reinterpret_cast<int32_t*>(d + o_st);
   int32_t* g2ok = reinterpret_cast<int32_t*>(d + o_g2ok);
   c.eidx = bn ? reinterpret_cast<const int32_t*>(d + o_eidx) : nullptr, c.g2ok = bn ? g2ok : nullptr;
-  c.tables = K->d_tables, c.hash = K->d_hash, c.lines = K->d_lines, c.msg = d + o_msg;
+  c.tables = K->d_tables.as<uint32_t>(), c.hash = K->d_hash.as<uint32_t>(), c.lines = K->d_lines.as<uint32_t>(), c.msg = d + o_msg;
   c.gok = reinterpret_cast<int32_t*>(scr + bp_gok_off(n, ng));
   c.cnt = reinterpret_cast<int32_t*>(scr + bp_cnt_off(n, ng));
   c.list = reinterpret_cast<int32_t*>(scr + bp_list_off(n, ng));
@@ -1639,7 +1588,7 @@ int fts_idemix_identity_verify_batch(fts_idemix_idv* K, size_t n, const uint8_t*
   D.stats[0] = K->batch ? (uint32_t)ng : 0u;
   D.stats[1] = K->batch ? nlist : (uint32_t)n;
   if (M) {
-    std::lock_guard<std::mutex> l(K->mu);
+    std::lock_guard<std::mutex> l(K->ring.mu);
     if (K->g2_seen.size() + M > 4096) K->g2_seen.clear();  // bounded: a new epoch's keys refill it
     for (size_t q = 0; q < M; q++) {
       const size_t j = (size_t)miss[q];
@@ -1653,14 +1602,14 @@ int fts_idemix_identity_verify_batch(fts_idemix_idv* K, size_t n, const uint8_t*
 
 int fts_idemix_identity_last_timings(fts_idemix_idv* K, float* ms) {
   if (!K || !ms) return FTS_API_EINVAL;
-  std::lock_guard<std::mutex> l(K->mu);
+  std::lock_guard<std::mutex> l(K->ring.mu);
   ms[0] = K->last_ms[0], ms[1] = K->last_ms[1];
   return FTS_API_OK;
 }
 
 int fts_idemix_identity_last_stats(fts_idemix_idv* K, uint32_t* out) {
   if (!K || !out) return FTS_API_EINVAL;
-  std::lock_guard<std::mutex> l(K->mu);
+  std::lock_guard<std::mutex> l(K->ring.mu);
   out[0] = K->last_stats[0], out[1] = K->last_stats[1];
   return FTS_API_OK;
 }
@@ -1679,26 +1628,23 @@ int fts_idemix_pairing_debug(fts_idemix_idv* K, int which, const uint8_t* p64, i
   } else {
     return FTS_API_EINVAL;  // FP256BN points go through fts_idemix_pairing_debug_mont
   }
-  std::lock_guard<std::mutex> l(K->mu);
+  std::lock_guard<std::mutex> l(K->ring.mu);
   ICHK(hipSetDevice(K->device));
   // private stream and buffers, released on every exit path
   struct Res {
-    uint32_t *p = nullptr, *o = nullptr;
-    hipStream_t s = nullptr;
+    Stream s;
+    DevBuf p, o;
     ~Res() {
       if (s) (void)hipStreamSynchronize(s);
-      if (p) (void)hipFree(p);
-      if (o) (void)hipFree(o);
-      if (s) (void)hipStreamDestroy(s);
     }
   } r;
-  ICHK(hipStreamCreateWithFlags(&r.s, hipStreamNonBlocking));
-  ICHK(hipMalloc(&r.p, 64));
-  ICHK(hipMalloc(&r.o, 192 * 4));
-  ICHK(hipMemcpyAsync(r.p, pm, 64, hipMemcpyHostToDevice, r.s));
-  k_idv_pairing_debug<BnCurve><<<1, 64, 0, r.s>>>(K->d_lines, which, r.p, r.o, final_exp);
+  ICHK(r.s.create());
+  if (!r.p.reserve(64) || !r.o.reserve(192 * 4)) return FTS_API_EDEVICE;
+  ICHK(hipMemcpyAsync(r.p.p, pm, 64, hipMemcpyHostToDevice, r.s));
+  k_idv_pairing_debug<BnCurve><<<1, 64, 0, r.s>>>(K->d_lines.as<uint32_t>(), which, r.p.as<uint32_t>(),
+                                                  r.o.as<uint32_t>(), final_exp);
   ICHK(hipGetLastError());
-  ICHK(hipMemcpyAsync(out192, r.o, 192 * 4, hipMemcpyDeviceToHost, r.s));
+  ICHK(hipMemcpyAsync(out192, r.o.p, 192 * 4, hipMemcpyDeviceToHost, r.s));
   ICHK(hipStreamSynchronize(r.s));
   return FTS_API_OK;
 }

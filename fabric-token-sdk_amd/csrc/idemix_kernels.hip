@@ -29,8 +29,8 @@
 
 #include <algorithm>
 #include <atomic>
-#include <condition_variable>
 #include <functional>
+#include <memory>
 #include <mutex>
 #include <thread>
 #include <vector>
@@ -43,6 +43,7 @@
 #include "device/transcript.hpp"
 #include "device/fp256bn.hpp"
 #include "host/bn254_host.hpp"
+#include "host/hip_owned.hpp"
 #include "host/pb.hpp"
 
 namespace fts {
@@ -598,12 +599,10 @@ constexpr int NSLOT = 3;
 // items per nym-kernel launch (the GLV lane tables are sized for one tile)
 constexpr size_t NYM_TILE = 262144;
 struct Slot {
-  hipStream_t stream = nullptr;
-  uint8_t* d_buf = nullptr;  // rec | nym | moff | mlen | status | vtab | messages
-  size_t d_cap = 0;
-  uint8_t* h_buf = nullptr;  // pinned staging of everything above but vtab
-  size_t h_cap = 0;
-  hipEvent_t ev[2] = {nullptr, nullptr};
+  Stream stream;
+  DevBuf d_buf;  // rec | nym | moff | mlen | status | vtab | messages
+  PinBuf h_buf;  // pinned staging of everything above but vtab
+  Event ev[2];
   float ms = 0.f;
 };
 
@@ -612,33 +611,18 @@ struct Slot {
 struct fts_idemix_ipk {
   int device = -1;
   int curve = 1;                 // mathlib CurveID: 1 BN254, 0 FP256BN_AMCL
-  uint32_t* d_tables = nullptr;  // HSk, HRand (FB_W-bit windows)
-  uint32_t* d_hash = nullptr;    // ipk.Hash as 8 big-endian words
+  DevBuf d_tables;               // HSk, HRand (FB_W-bit windows)
+  DevBuf d_hash;                 // ipk.Hash as 8 big-endian words
   uint8_t hash[32];
-  std::mutex mu;
-  std::condition_variable cv;
-  Slot slot[NSLOT];
-  bool busy[NSLOT] = {false, false, false};
-  float last_ms = 0.f;
+  SlotRing<Slot, NSLOT> ring;
+  float last_ms = 0.f;     // under ring.mu
   size_t tile = NYM_TILE;  // items per launch (FTS_NYM_TILE overrides, for tests)
+  ~fts_idemix_ipk() {
+    if (device >= 0) (void)hipSetDevice(device);
+  }
 };
 
 namespace {
-void ipk_free(fts_idemix_ipk* k) {
-  if (!k) return;
-  if (k->device >= 0) (void)hipSetDevice(k->device);
-  for (auto& S : k->slot) {
-    if (S.stream) (void)hipStreamSynchronize(S.stream), (void)hipStreamDestroy(S.stream);
-    for (auto& e : S.ev)
-      if (e) (void)hipEventDestroy(e);
-    if (S.d_buf) (void)hipFree(S.d_buf);
-    if (S.h_buf) (void)hipHostFree(S.h_buf);
-  }
-  if (k->d_tables) (void)hipFree(k->d_tables);
-  if (k->d_hash) (void)hipFree(k->d_hash);
-  delete k;
-}
-
 // ECP{x, y} -> affine Montgomery point (host), on-curve checked
 bool ecp_point(const uint8_t* v, size_t vl, host::G1A& out) {
   Pb pb{v, vl};
@@ -710,18 +694,14 @@ int fts_idemix_ipk_create(int device, const uint8_t* ipk, size_t ipk_len, int cu
   }
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return FTS_API_EDEVICE;
-  fts_idemix_ipk* k = new fts_idemix_ipk();
+  std::unique_ptr<fts_idemix_ipk> k(new fts_idemix_ipk());
   k->device = device;
   k->curve = curve_id;
   if (const char* e = getenv("FTS_NYM_TILE")) k->tile = (size_t)std::max(64L, std::min((long)NYM_TILE, atol(e)));
   // copy(proofData[index:], ipk.Hash) into a FieldBytes window
   memset(k->hash, 0, 32);
   if (hash) memcpy(k->hash, hash, std::min<size_t>(hashl, 32));
-  auto fail = [&](int rc) {
-    ipk_free(k);
-    return rc;
-  };
-  if (hipSetDevice(device) != hipSuccess) return fail(FTS_API_EDEVICE);
+  if (hipSetDevice(device) != hipSuccess) return FTS_API_EDEVICE;
   uint32_t hb[32];
   for (int b = 0; b < 2; b++) {
     memcpy(&hb[b * 16], base[b].x.v, 32);
@@ -731,20 +711,21 @@ int fts_idemix_ipk_create(int device, const uint8_t* ipk, size_t ipk_len, int cu
   for (int q = 0; q < 8; q++)
     hw[q] = ((uint32_t)k->hash[4 * q] << 24) | ((uint32_t)k->hash[4 * q + 1] << 16) |
             ((uint32_t)k->hash[4 * q + 2] << 8) | k->hash[4 * q + 3];
-  uint32_t* d_bases = nullptr;
-  uint32_t* d_scr = nullptr;
-  hipStream_t s0 = nullptr;
+  DevBuf bases_buf, scr_buf;
+  Stream s0;
   const bool bn = curve_id == FTS_CURVE_BN254;
   const size_t tab_b = bn ? 2 * fb_words_per_base() * 4 : (size_t)2 * FBN_NW * FBN_ND * 16 * 4;
   const size_t scr_b = bn ? table_build_scratch_bytes(2) : 2 * 16 * 4 + 64;
-  bool ok = hipStreamCreateWithFlags(&s0, hipStreamNonBlocking) == hipSuccess &&
-            hipMalloc(&k->d_tables, tab_b) == hipSuccess && hipMalloc(&k->d_hash, 32) == hipSuccess &&
-            hipMalloc(&d_bases, sizeof(hb)) == hipSuccess && hipMalloc(&d_scr, scr_b) == hipSuccess &&
-            hipMemcpyAsync(d_bases, bn ? hb : plain, sizeof(hb), hipMemcpyHostToDevice, s0) == hipSuccess &&
-            hipMemcpyAsync(k->d_hash, hw, 32, hipMemcpyHostToDevice, s0) == hipSuccess;
+  bool ok = s0.create() == hipSuccess && k->d_tables.reserve(tab_b) && k->d_hash.reserve(32) &&
+            bases_buf.reserve(sizeof(hb)) && scr_buf.reserve(scr_b);
+  uint32_t* const d_tables = k->d_tables.as<uint32_t>();
+  uint32_t* const d_bases = bases_buf.as<uint32_t>();
+  uint32_t* const d_scr = scr_buf.as<uint32_t>();
+  ok = ok && hipMemcpyAsync(d_bases, bn ? hb : plain, sizeof(hb), hipMemcpyHostToDevice, s0) == hipSuccess &&
+       hipMemcpyAsync(k->d_hash.p, hw, 32, hipMemcpyHostToDevice, s0) == hipSuccess;
   bool on_curve = true;
   if (ok && bn) {
-    launch_build_tables(d_bases, 2, k->d_tables, d_scr, s0);
+    launch_build_tables(d_bases, 2, d_tables, d_scr, s0);
     ok = hipGetLastError() == hipSuccess && hipStreamSynchronize(s0) == hipSuccess;
   } else if (ok) {
     // plain -> Montgomery + on-curve flags (into the scratch), then the window tables
@@ -758,28 +739,22 @@ int fts_idemix_ipk_create(int device, const uint8_t* ipk, size_t ipk_len, int cu
     on_curve = hf[0] == 1 && hf[1] == 1;
     if (ok && on_curve) {
       const size_t ent = (size_t)2 * FBN_NW * FBN_ND;
-      k_fbn_table<<<(unsigned)((ent + 255) / 256), 256, 0, s0>>>(2, mont, k->d_tables);
+      k_fbn_table<<<(unsigned)((ent + 255) / 256), 256, 0, s0>>>(2, mont, d_tables);
       ok = hipGetLastError() == hipSuccess && hipStreamSynchronize(s0) == hipSuccess;
     }
   }
   if (s0) (void)hipStreamSynchronize(s0);  // an error path may leave copies queued on s0
-  if (d_bases) (void)hipFree(d_bases);
-  if (d_scr) (void)hipFree(d_scr);
-  if (ok && !on_curve) {
-    if (s0) (void)hipStreamDestroy(s0);
-    return fail(FTS_API_EPP);
+  if (ok && !on_curve) return FTS_API_EPP;
+  for (auto& S : k->ring.slot) {
+    ok = ok && S.stream.create() == hipSuccess;
+    for (auto& e : S.ev) ok = ok && e.create() == hipSuccess;
   }
-  if (s0) (void)hipStreamDestroy(s0);
-  for (auto& S : k->slot) {
-    ok = ok && hipStreamCreateWithFlags(&S.stream, hipStreamNonBlocking) == hipSuccess;
-    for (auto& e : S.ev) ok = ok && hipEventCreate(&e) == hipSuccess;
-  }
-  if (!ok) return fail(FTS_API_EDEVICE);
-  *out = k;
+  if (!ok) return FTS_API_EDEVICE;
+  *out = k.release();
   return FTS_API_OK;
 }
 
-void fts_idemix_ipk_destroy(fts_idemix_ipk* k) { ipk_free(k); }
+void fts_idemix_ipk_destroy(fts_idemix_ipk* k) { delete k; }
 
 int fts_idemix_identity_nym(const uint8_t* id, size_t len, const uint8_t** nym, size_t* nym_len) {
   if (!id || !nym || !nym_len) return FTS_API_EINVAL;
@@ -811,30 +786,8 @@ int fts_nym_verify_batch(fts_idemix_ipk* K, size_t n, const fts_nym_item* items,
     if (items[i].msg_len > 0xffffff00u || (items[i].msg_len && !items[i].msg)) return FTS_API_EINVAL;
     mtot_w += (pre + items[i].msg_len + 3) / 4 + 1;
   }
-  int k = -1;
-  {
-    std::unique_lock<std::mutex> l(K->mu);
-    K->cv.wait(l, [&] {
-      for (int j = 0; j < NSLOT; j++)
-        if (!K->busy[j]) return true;
-      return false;
-    });
-    for (int j = 0; j < NSLOT && k < 0; j++)
-      if (!K->busy[j]) k = j;
-    K->busy[k] = true;
-  }
-  struct Guard {
-    fts_idemix_ipk* K;
-    int k;
-    ~Guard() {
-      if (K->slot[k].stream) (void)hipStreamSynchronize(K->slot[k].stream);
-      std::lock_guard<std::mutex> l(K->mu);
-      K->last_ms = K->slot[k].ms;
-      K->busy[k] = false;
-      K->cv.notify_one();
-    }
-  } guard{K, k};
-  Slot& D = K->slot[k];
+  auto guard = K->ring.acquire([K](Slot& S) { K->last_ms = S.ms; });
+  Slot& D = guard.slot();
   ICHK(hipSetDevice(K->device));
   // layout: rec | nym | moff | mlen | status | messages (| vtab on the device only)
   const size_t rec_b = n * NREC * 4, nym_b = n * 64, off_b = n * 8, len_b = n * 4, st_b = n * 4;
@@ -846,19 +799,9 @@ int fts_nym_verify_batch(fts_idemix_ipk* K, size_t n, const fts_nym_item* items,
   // asked for ~38 GB here)
   const size_t tile = std::min<size_t>(n, K->tile);
   const size_t vt_b = tile * 16 * 24 * 4, o_vt = (h_need + 255) & ~size_t(255), d_need = o_vt + vt_b;
-  if (D.h_cap < h_need) {
-    if (D.h_buf) (void)hipHostFree(D.h_buf);
-    D.h_buf = nullptr, D.h_cap = 0;
-    if (hipHostMalloc(&D.h_buf, h_need + h_need / 2, hipHostMallocDefault) != hipSuccess) return FTS_API_ENOMEM;
-    D.h_cap = h_need + h_need / 2;
-  }
-  if (D.d_cap < d_need) {
-    if (D.d_buf) (void)hipFree(D.d_buf);
-    D.d_buf = nullptr, D.d_cap = 0;
-    if (hipMalloc(&D.d_buf, d_need + d_need / 2) != hipSuccess) return FTS_API_ENOMEM;
-    D.d_cap = d_need + d_need / 2;
-  }
-  uint8_t* h = D.h_buf;
+  if (D.h_buf.cap < h_need && !D.h_buf.reserve(h_need + h_need / 2)) return FTS_API_ENOMEM;
+  if (D.d_buf.cap < d_need && !D.d_buf.reserve(d_need + d_need / 2)) return FTS_API_ENOMEM;
+  uint8_t* h = D.h_buf.as<uint8_t>();
   uint64_t* hoff = reinterpret_cast<uint64_t*>(h + o_off);
   {
     uint64_t o = 0;
@@ -894,7 +837,7 @@ int fts_nym_verify_batch(fts_idemix_ipk* K, size_t n, const fts_nym_item* items,
   };
   const size_t CH = 2048, nch = (n + CH - 1) / CH;
   fts::host_parallel_for(nch, [&](size_t c) { pack(c * CH, std::min(n, (c + 1) * CH)); });
-  uint8_t* d = D.d_buf;
+  uint8_t* d = D.d_buf.as<uint8_t>();
   ICHK(hipMemcpyAsync(d, h, h_need, hipMemcpyHostToDevice, D.stream));
   ICHK(hipEventRecord(D.ev[0], D.stream));
   for (size_t base = 0; base < n; base += tile) {
@@ -902,14 +845,15 @@ int fts_nym_verify_batch(fts_idemix_ipk* K, size_t n, const fts_nym_item* items,
     if (bn)
       k_nym_verify<<<grid, 256, 0, D.stream>>>(
           (int)n, reinterpret_cast<const uint32_t*>(d), d + o_nym, reinterpret_cast<const uint32_t*>(d + o_msg),
-          reinterpret_cast<const uint64_t*>(d + o_off), reinterpret_cast<const uint32_t*>(d + o_len), K->d_tables,
-          K->d_hash, reinterpret_cast<uint32_t*>(d + o_vt), reinterpret_cast<int32_t*>(d + o_st), (int)base,
+          reinterpret_cast<const uint64_t*>(d + o_off), reinterpret_cast<const uint32_t*>(d + o_len),
+          K->d_tables.as<uint32_t>(), K->d_hash.as<uint32_t>(), reinterpret_cast<uint32_t*>(d + o_vt), reinterpret_cast<int32_t*>(d + o_st), (int)base,
           (int)tile);
     else
       k_nym_verify_fbn<<<grid, 256, 0, D.stream>>>(
           (int)n, reinterpret_cast<const uint32_t*>(d), d + o_nym, reinterpret_cast<const uint32_t*>(d + o_msg),
-          reinterpret_cast<const uint64_t*>(d + o_off), reinterpret_cast<const uint32_t*>(d + o_len), K->d_tables,
-          reinterpret_cast<uint32_t*>(d + o_vt), reinterpret_cast<int32_t*>(d + o_st), (int)base, (int)tile);
+          reinterpret_cast<const uint64_t*>(d + o_off), reinterpret_cast<const uint32_t*>(d + o_len),
+          K->d_tables.as<uint32_t>(), reinterpret_cast<uint32_t*>(d + o_vt), reinterpret_cast<int32_t*>(d + o_st),
+          (int)base, (int)tile);
   }
   ICHK(hipGetLastError());
   ICHK(hipEventRecord(D.ev[1], D.stream));
@@ -922,7 +866,7 @@ int fts_nym_verify_batch(fts_idemix_ipk* K, size_t n, const fts_nym_item* items,
 
 int fts_nym_last_timings(fts_idemix_ipk* K, float* ms) {
   if (!K || !ms) return FTS_API_EINVAL;
-  std::lock_guard<std::mutex> l(K->mu);
+  std::lock_guard<std::mutex> l(K->ring.mu);
   *ms = K->last_ms;
   return FTS_API_OK;
 }

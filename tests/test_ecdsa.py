@@ -133,6 +133,19 @@ def test_gpu_golden():
 
 
 @pytest.mark.gpu
+def test_gpu_regrow_after_shrink():
+    """Calls of 3, 300 and 3 items in turn: the staging slot's buffers re-allocate
+    (300 is past the 1.5x headroom of a 3-item allocation), then serve a smaller
+    call; every verdict is the fixture's."""
+    from fts_gpu import ecdsa as E
+    for n in (3, 300, 3):
+        cs = [GOLD[i % len(GOLD)] for i in range(n)]
+        ms, ss, ps = zip(*[_case(c) for c in cs])
+        st = E.verify_batch(ms, ss, ps, device=0)
+        assert [int(x) for x in st] == [c["expect"] for c in cs]
+
+
+@pytest.mark.gpu
 def test_gpu_crafted_r_plus_n():
     """accept iff X.x == r or X.x == r + n (< p): the r + n branch is reached only by
     crafted signatures (ecdsa_kernels.hip final check)"""

@@ -129,6 +129,34 @@ def test_transfer_batch_mixed(gpu_pp, oracle_pp):
     assert [(int(s), int(i)) for s, i in zip(st, fi)] == expect
 
 
+def test_transfers_regrow_after_shrink(pp_raw, oracle_pp):
+    """3, 300 and 3 transfers on a fresh 8-bit context: the action slot is allocated,
+    re-allocated (300 is past the 1.5x headroom), then reused by a smaller call.
+    Three distinct transfers (honest, wrong sum, 1-in/1-out) repeated; each verdict
+    is the oracle's for its pattern."""
+    import fts_gpu
+    pp = fts_gpu.PublicParams(pp_raw, bit_length=8, device=0)
+    opp = oracle_pp.with_bit_length(8)
+    T = b"ABC"
+    try:
+        pat = []
+        for seed, (inv, outv) in enumerate((([100, 20], [70, 50]), ([100, 20], [70, 51]), ([5], [5])), 1):
+            ib = [_bf(seed * 10 + j) for j in range(len(inv))]
+            ob = [_bf(seed * 10 + 5 + j) for j in range(len(outv))]
+            ins = [pp.token_commit(T, v, b) for v, b in zip(inv, ib)]
+            outs = [pp.token_commit(T, v, b) for v, b in zip(outv, ob)]
+            proof = pp.prove_transfer(T, inv, ib, outv, ob, seed)
+            err, idx = zkat.transfer_verify(opp, [bn.g1_from_bytes(x) for x in ins],
+                                            [bn.g1_from_bytes(x) for x in outs], proof)
+            pat.append(((ins, outs, proof), oracle_status(err, idx)))
+        assert pat[0][1] == (0, -1) and pat[1][1][0] == 8 and pat[2][1] == (0, -1)
+        for n in (3, 300, 3):
+            st, fi = pp.verify_transfers([pat[i % 3][0] for i in range(n)])
+            assert [(int(s), int(i)) for s, i in zip(st, fi)] == [pat[i % 3][1] for i in range(n)]
+    finally:
+        pp.close()
+
+
 def test_issue_batch_mixed(gpu_pp, oracle_pp):
     import fts_gpu
     bits = 8

@@ -182,6 +182,26 @@ def test_empty_and_single(gpu_pp):
     assert list(pp.verify_range_proofs([raw], [com])) == [0]
 
 
+def test_regrow_after_shrink_on_one_context(pp_raw, oracle_pp):
+    """fts_rp_verify_batch with 3, 300 and 3 proofs on a fresh context: the staging
+    slot and the lane workspace are allocated, re-allocated (300 is past the 1.5x
+    headroom), then reused by a smaller call; verdicts equal the C oracle's"""
+    import fts_gpu
+    from oracle import cref
+    pp = fts_gpu.PublicParams(pp_raw, bit_length=8, device=0)
+    opp = oracle_pp.with_bit_length(8)
+    try:
+        proofs, coms = pp.prove_range_batch([i % 256 for i in range(300)], [(i + 9).to_bytes(32, "big") for i in range(300)], 3)
+        for i in (1, 2, 150, 299):  # another proof's bytes: fails against this commitment
+            proofs[i] = proofs[i - 1]
+        want = cref.rp_verify_many(opp, coms, proofs, threads=1)
+        assert want[0] == 0 and want[1] != 0 and want[299] != 0
+        for n in (3, 300, 3):
+            assert [int(s) for s in pp.verify_range_proofs(proofs[:n], coms[:n])] == want[:n]
+    finally:
+        pp.close()
+
+
 def test_staged_batch_reverifies(gpu_pp):
     pp = gpu_pp(16)
     proofs, coms = pp.prove_range_batch(list(range(1000, 1064)), [(i + 5).to_bytes(32, "big") for i in range(64)], 5)

@@ -76,6 +76,22 @@ def test_golden_verdicts(ipk_dev):
 
 
 @pytest.mark.gpu
+def test_regrow_after_shrink_on_one_handle():
+    """3, 300, 3 signatures on a fresh handle: the slot's buffers are allocated,
+    re-allocated (300 is past the 1.5x headroom), then reused by a smaller call"""
+    from fts_gpu import idemix as I
+    k = I.IssuerKey(IPK, device=0)
+    try:
+        for n in (3, 300, 3):
+            cs = [GOLD["cases"][i % len(GOLD["cases"])] for i in range(n)]
+            st = k.verify_batch([bytes.fromhex(c["nym"]) for c in cs], [bytes.fromhex(c["sig"]) for c in cs],
+                                [bytes.fromhex(c["msg"]) for c in cs])
+            assert [I.message(int(s)) for s in st] == [c["error"] for c in cs]
+    finally:
+        k.close()
+
+
+@pytest.mark.gpu
 def test_golden_verdicts_fp256bn(ipk_fbn):
     _golden(ipk_fbn, GOLD_FBN)
 

@@ -47,6 +47,22 @@ def test_golden_identity_verdicts(verifiers, tag):
     assert got == want
 
 
+def test_regrow_after_shrink_on_one_handle():
+    """3, 300, 3 identities on a fresh handle: the slot's buffers are allocated,
+    re-allocated (300 is past the 1.5x headroom), then reused by a smaller call"""
+    from fts_gpu import idemix as I
+    doc = _doc()["bn254"]
+    pool = doc["cases"] + doc["tile"]
+    v = I.IdentityVerifier(_ipk(doc["issuer"]), device=0, curve=doc["curve_id"])
+    try:
+        for n in (3, 300, 3):
+            cs = [pool[i % len(pool)] for i in range(n)]
+            st = v.verify_batch([bytes.fromhex(c["identity"]) for c in cs])
+            assert [I.message(int(s)) for s in st] == [c["error"] for c in cs]
+    finally:
+        v.close()
+
+
 @pytest.mark.parametrize("tag", ["bn254", "fp256bn"])
 def test_single_identity_api(verifiers, tag):
     from fts_gpu import idemix as I

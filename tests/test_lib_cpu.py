@@ -4,6 +4,7 @@ reference-format proofs that the independent oracle accepts (and rejects when
 the statement is false) — no GPU compute here."""
 import os
 import re
+import subprocess
 
 import pytest
 
@@ -25,6 +26,15 @@ def test_exports_every_header_symbol():
     for n in names:
         assert hasattr(L.lib, n), n
     assert set(names) == set(L.EXPORTED)
+
+
+def test_owned_types_check():
+    """lib/owned_check (csrc/tools/owned_check.cpp): the owning HIP types of
+    host/hip_owned.hpp and the slot ring, exercised with or without a device"""
+    exe = os.path.join(ROOT, "fabric-token-sdk_amd", "lib", "owned_check")
+    out = subprocess.run([exe], capture_output=True, text=True, timeout=60)
+    assert out.returncode == 0, out.stdout + out.stderr
+    assert "owned_check: ok" in out.stdout
 
 
 def test_status_strings():
