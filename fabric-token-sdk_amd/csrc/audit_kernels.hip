@@ -20,6 +20,7 @@
 #include "device/fixed_base.hpp"
 #include "device/helpers.hpp"
 #include "device/rp_kernels.hpp"
+#include "device/launch.hpp"
 #include "../../include/fts_gpu.h"
 
 namespace fts {

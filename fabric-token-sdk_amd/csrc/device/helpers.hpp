@@ -14,7 +14,7 @@ namespace fts {
 // slots (r05 trace: k_msm_scan1 0.005 ms alone, 0.64 ms beside com_var; the MSM's sort
 // 0.5 ms alone, 5.9 ms in the pass).  One static level per kernel group, set once at
 // kernel entry from this table (a uniform scalar load; FTS_WAVE_PRIO overrides it per
-// context, fts_api.cpp).
+// context, api_ctx.cpp).
 static __constant__ int g_wave_prio[PS_N] = FTS_WAVE_PRIO_DEFAULT;
 template <int S>
 FTS_DEV void wave_prio() {

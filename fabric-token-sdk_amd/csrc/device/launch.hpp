@@ -1,0 +1,97 @@
+// Everything one translation unit defines and another uses: the kernel
+// launchers, their size functions and the process-wide launch knobs.  Included
+// by the unit that defines a name and by every unit that uses it, so a changed
+// parameter, default argument or variable type fails to compile instead of
+// surfacing at link time (or never).  The structures are only named here; a
+// unit includes the header that defines the ones it touches.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stddef.h>
+#include <stdint.h>
+#include <atomic>
+
+namespace fts {
+
+struct MsmPlan;
+struct PvDev;
+struct PvStage;
+struct RlcDev;
+struct RpBatchDev;
+struct RpGather;
+struct SigBatchDev;
+struct SpDev;
+struct Timeline;
+
+// ---- the host API (api_ctx.cpp)
+// "fb:" + nm, interned (Timeline marks after fallback())
+const char* fallback_name(const char* nm);
+
+// ---- rp_kernels.hip
+extern int g_lat_bs;                // block size of the latency-bound per-proof kernels
+extern std::atomic<int> g_work_bs;  // FTS_WORK_BS: written by context creation while other lanes launch
+size_t rp_scratch_words(int B, int n, int k);
+size_t rp_terms_words(int B, int n, int k);
+size_t fb_words_per_base();
+size_t fbw_words_per_base(int wbits);
+size_t table_build_scratch_bytes(int nb);
+size_t wide_build_scratch_bytes(int nb, int wbits);
+void launch_build_tables(const uint32_t* bases, int nb, uint32_t* tables, uint32_t* scratch, hipStream_t s);
+void launch_build_wide_tables(const uint32_t* bases, int nb, uint32_t* tables, uint32_t* scratch, hipStream_t s,
+                              int wbits);
+void launch_rp_batch(const RpBatchDev& d, const RlcDev& r, const uint32_t* tables, const uint32_t* wtables,
+                     const uint8_t* x0_const, const uint8_t* x0_tmpl, hipStream_t s, hipStream_t s2, hipStream_t s3,
+                     hipStream_t s4, Timeline* tl, int wbits);
+void launch_rp_fallback(const RpBatchDev& d, const uint32_t* tables, const int32_t* sel, int nsel, hipStream_t s,
+                        Timeline* tl);
+void launch_rlc_group_test(const RpBatchDev& d, const RlcDev& r, const uint32_t* tables, const MsmPlan& p,
+                           const int32_t* sel, int G, int gs, uint32_t* gcol, uint32_t* gfix, int32_t* next,
+                           uint32_t* next_count, hipStream_t s, Timeline* tl);
+void launch_rp_gather(const RpGather& g, int k, uint8_t* raw, uint32_t* sc, int32_t* status, int32_t* ipa,
+                      hipStream_t s);
+void launch_rlc_locate(const RpBatchDev& d, const RlcDev& r, const uint32_t* tables, uint32_t* save, int32_t* loc,
+                       hipStream_t s, Timeline* tl);
+void launch_rlc_accept_except(int B, int skip, int32_t* status, const int32_t* ipa_flag, hipStream_t s);
+void launch_normalize_all(int total, const uint32_t* jac, uint32_t* aff, hipStream_t s);
+void launch_msm_gen_points(int N, const uint8_t* raw_k, const uint8_t* raw_s, const uint32_t* table, uint32_t* jac,
+                           uint32_t* pts, uint32_t* sc, hipStream_t s);
+void launch_x0(int B, int n, int k, const int32_t* status, const uint8_t* hp_be, const uint8_t* x0_const,
+               const uint8_t* x0_tmpl, const uint32_t* sc, uint8_t* msgs, uint32_t* ch, hipStream_t s);
+// wave priority table (helpers.hpp PrioSlot) of rp_kernels.hip's and msm.hip's kernels
+hipError_t rp_set_wave_prio(const int* p);
+hipError_t msm_set_wave_prio(const int* p);
+
+// ---- msm.hip
+// ev_stage (optional): recorded on s after the counting sort (stage 1) or the bucket
+// accumulation (stage 2)
+void launch_msm(const MsmPlan& p, const uint32_t* points, const uint32_t* scalars, const uint32_t* extra, int nextra,
+                uint32_t* scratch, hipStream_t s, hipStream_t s_extra, Timeline* tl, hipEvent_t ev_stage = nullptr,
+                int stage = 0);
+void launch_msm_small(const MsmPlan& p, const uint32_t* points, const uint32_t* scalars, const uint32_t* extra,
+                      int nextra, hipStream_t s, Timeline* tl);
+void launch_msm_sort(const MsmPlan& p, const uint32_t* scalars, hipStream_t s, Timeline* tl);
+void launch_msm_reduce(const MsmPlan& p, const uint32_t* points, const uint32_t* extra, int nextra, uint32_t* scratch,
+                       hipStream_t s, hipStream_t s_extra, Timeline* tl);
+void launch_msm_load(int N, const uint8_t* raw_pts, const uint8_t* raw_sc, uint32_t* pts, uint32_t* sc, uint32_t* bad,
+                     hipStream_t s);
+void launch_msm_to_bytes(const uint32_t* jac, uint8_t* out, hipStream_t s);
+void launch_msm_pts_to_bytes(int n, const uint32_t* pts, uint8_t* out, hipStream_t s);
+
+// ---- sigma_kernels.hip
+void launch_sig_prep(const SigBatchDev& d, hipStream_t s);
+void launch_sig_finish(const SigBatchDev& d, const uint32_t* tables, int n, hipStream_t s);
+void launch_sig_exclude(const SigBatchDev& d, int32_t* rp_excl, hipStream_t s);
+
+// ---- prove_kernels.hip
+void launch_rp_prove(const PvDev& d, const PvStage* stages, const uint8_t* x0_const, const uint8_t* x0_tmpl,
+                     hipStream_t s, Timeline* tl);
+void launch_sigma_prove(const SpDev& d, hipStream_t s);
+
+// ---- audit_kernels.hip
+void launch_open_check(int n, const uint8_t* raw, const uint32_t* sc, const uint32_t* tables, int nb,
+                       int32_t* status, hipStream_t s);
+
+// ---- idemix_kernels.hip (FP256BN fixed-base tables, shared with idemix_identity.hip)
+void fbn_build_tables(const uint32_t* plain, int nb, uint32_t* mont, int32_t* ok, uint32_t* tables, hipStream_t s);
+size_t fbn_words_per_base();
+
+}  // namespace fts

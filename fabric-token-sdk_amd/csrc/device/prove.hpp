@@ -1,5 +1,5 @@
 // Layout shared by the batched range-proof prover kernels (prove_kernels.hip)
-// and the host driver (fts_api.cpp).
+// and the host driver (api_prove.cpp).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "launch.hpp"
 
 namespace fts {
 
@@ -90,7 +91,6 @@ constexpr double COST_NORM = 7.0;
 // events start the next kernel's interval on the waiting stream).
 // Marks made after fallback() (the batch check's group test and per-proof
 // checks) are reported under "fb:" names, apart from the main pass's kernels.
-const char* fallback_name(const char* nm);
 struct Timeline {
   static constexpr int CAP = 96;
   bool in_fallback = false;
@@ -155,7 +155,7 @@ struct Timeline {
   }
 };
 
-// device buffers of one range-proof batch (filled by fts_api.cpp)
+// device buffers of one range-proof batch (filled by api_rp.cpp)
 // staged batches gathered into one device pass (fts_rp_batch_verify coalescing)
 constexpr int RP_GATHER_MAX = 32;
 struct RpGather {
@@ -190,7 +190,7 @@ struct RpBatchDev {
   int com_fixed;       // 1: com by fixed-base groups + x*D on the side stream (latency path,
                        //    small passes); 0: Horner sum + joint GLV/Straus chains (work path)
   int rlc_fork = 1;    // batch check's stream forks after the fixed-base products (1) or after the challenges (0);
-                       //    fts_api.cpp picks 0 on the latency path, 1 on the work path (FTS_RLC_FORK=2)
+                       //    api_rp.cpp picks 0 on the latency path, 1 on the work path (FTS_RLC_FORK=2)
   hipEvent_t ev_coef = nullptr;  // recorded on the check's stream after k_rlc_prep (column Q on s waits for it)
   hipEvent_t ev_fx = nullptr;    // recorded on s after the fixed-base launch (rlc_fork 3: the MSM accumulation waits;
                                  // FTS_FX_SERIAL: the next pass's fixed-base launch waits)

@@ -34,6 +34,7 @@
 #include "common/sha256.hpp"
 #include "device/p256.hpp"
 #include "host/hip_owned.hpp"
+#include "host/host_pool.hpp"
 
 using namespace p256;
 using fts::DevBuf;
@@ -41,10 +42,6 @@ using fts::Event;
 using fts::PinBuf;
 using fts::SlotRing;
 using fts::Stream;
-
-namespace fts {
-void host_parallel_for(size_t n, const std::function<void(size_t)>& f);  // fts_api.cpp (persistent host pool)
-}
 
 namespace {
 

@@ -153,7 +153,7 @@ struct ProverTables {
   const FixedBase& Q() const { return fb[2 * n + 4]; }
 };
 
-void build_prover_tables(const PublicParams& pp, int n, ProverTables& t);  // multi-threaded (api.cpp)
+void build_prover_tables(const PublicParams& pp, int n, ProverTables& t);  // multi-threaded (api_ctx.cpp)
 
 // sum_i s_i * base_i over fixed-base tables
 struct Msm {

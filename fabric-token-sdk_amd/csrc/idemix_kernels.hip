@@ -42,21 +42,13 @@
 #include "device/helpers.hpp"
 #include "device/transcript.hpp"
 #include "device/fp256bn.hpp"
+#include "device/launch.hpp"
 #include "host/bn254_host.hpp"
 #include "host/hip_owned.hpp"
+#include "host/host_pool.hpp"
 #include "host/pb.hpp"
 
-namespace fts {
-void launch_build_tables(const uint32_t* bases, int nb, uint32_t* tables, uint32_t* scratch, hipStream_t s);
-size_t table_build_scratch_bytes(int nb);
-size_t fb_words_per_base();
-}  // namespace fts
-
 using namespace fts;
-
-namespace fts {
-void host_parallel_for(size_t n, const std::function<void(size_t)>& f);  // fts_api.cpp (persistent host pool)
-}
 
 namespace {
 

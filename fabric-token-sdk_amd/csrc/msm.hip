@@ -14,9 +14,9 @@
 #include "device/msm.hpp"
 #include "device/rp_kernels.hpp"
 #include "device/coop.hpp"
+#include "device/launch.hpp"
 
 namespace fts {
-extern int g_lat_bs;  // rp_kernels.hip
 
 
 // bits [off, off+width) of a 128-bit LE magnitude (width <= 20)

@@ -26,6 +26,7 @@
 #include "device/rp_kernels.hpp"
 #include "device/transcript.hpp"
 #include "device/prove.hpp"
+#include "device/launch.hpp"
 
 namespace fts {
 
@@ -339,9 +340,6 @@ __global__ void __launch_bounds__(64) k_pv_lr(PvDev d, int j) {
 }
 
 // ------------------------------------------------------------------ launch
-void launch_x0(int B, int n, int k, const int32_t* status, const uint8_t* hp_be, const uint8_t* x0_const,
-               const uint8_t* x0_tmpl, const uint32_t* sc, uint8_t* msgs, uint32_t* ch, hipStream_t s);
-
 static void pv_sum(const PvDev& d, const PvStage& s, hipStream_t st) {
   hipLaunchKernelGGL(k_pv_fbsum, dim3((unsigned)((d.B * s.G + 63) / 64)), dim3(64), 0, st, d, s);
   hipLaunchKernelGGL(k_pv_segsum, dim3((unsigned)((d.B * s.S + 63) / 64)), dim3(64), 0, st, d, s);

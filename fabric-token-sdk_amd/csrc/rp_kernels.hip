@@ -33,6 +33,7 @@
 #include "device/helpers.hpp"
 #include "device/msm.hpp"
 #include "device/coop.hpp"
+#include "device/launch.hpp"
 #include "common/chacha20.hpp"
 #include "../../include/fts_gpu.h"
 
@@ -1632,7 +1633,7 @@ size_t rp_terms_words(int B, int n, int k) { return (size_t)B * rp_nterms(n, k) 
 
 size_t fb_words_per_base() { return FB_WORDS_PER_BASE; }
 // the per-proof bases' wide tables: 20-bit windows (13 per scalar, 436 MiB per base)
-// or 22-bit (12, 1.5 GiB per base) where the device has the memory (fts_api.cpp)
+// or 22-bit (12, 1.5 GiB per base) where the device has the memory (api_ctx.cpp)
 size_t fbw_words_per_base(int wbits) { return wbits == 22 ? FbCfg<22>::WORDS_PER_BASE : FbWide::WORDS_PER_BASE; }
 template <int W>
 static size_t build_scratch_bytes(int nb) {
@@ -1667,17 +1668,6 @@ void launch_build_wide_tables(const uint32_t* bases, int nb, uint32_t* tables, u
   if (wbits == 22) build_tables<22>(bases, nb, tables, scratch, s);
   else build_tables<FBW_W>(bases, nb, tables, scratch, s);
 }
-
-// ev_stage (optional): recorded on s after the counting sort (stage 1) or the bucket
-// accumulation (stage 2)
-void launch_msm(const MsmPlan& p, const uint32_t* points, const uint32_t* scalars, const uint32_t* extra, int nextra,
-                uint32_t* scratch, hipStream_t s, hipStream_t s_extra, Timeline* tl, hipEvent_t ev_stage = nullptr,
-                int stage = 0);
-void launch_msm_small(const MsmPlan& p, const uint32_t* points, const uint32_t* scalars, const uint32_t* extra,
-                      int nextra, hipStream_t s, Timeline* tl);
-void launch_msm_sort(const MsmPlan& p, const uint32_t* scalars, hipStream_t s, Timeline* tl);
-void launch_msm_reduce(const MsmPlan& p, const uint32_t* points, const uint32_t* extra, int nextra, uint32_t* scratch,
-                       hipStream_t s, hipStream_t s_extra, Timeline* tl);
 
 // Whole range-proof pipeline up to the batch verdict (flag): exact per-proof
 // phase (everything that is hashed: challenges, H'_i, com, x0) and the

@@ -16,6 +16,7 @@
 #include "device/rp_kernels.hpp"
 #include "device/sigma.hpp"
 #include "device/transcript.hpp"
+#include "device/launch.hpp"
 #include "../../include/fts_gpu.h"
 
 namespace fts {
@@ -238,8 +239,6 @@ __global__ void __launch_bounds__(64) k_sig_finish(int A, const SigAction* __res
   } while (0)
 
 // batch affine normalisation (rp_kernels.hip): all naff slots of the sigma batch
-void launch_normalize_all(int total, const uint32_t* jac, uint32_t* aff, hipStream_t s);
-
 // phase 1 (before the range-proof batch): decode + primes (writes the rp V slots)
 void launch_sig_prep(const SigBatchDev& d, hipStream_t s) {
   FTS_LAUNCH(k_sig_decode, d.npts, 256, s, d.npts, d.raw, d.pt_owner, d.pts, d.status);

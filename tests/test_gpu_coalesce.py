@@ -1,4 +1,4 @@
-"""GPU: action calls coalesced into shared device passes (fts_api.cpp act_stage /
+"""GPU: action calls coalesced into shared device passes (api_actions.cpp act_stage /
 rp_dispatch / run_rp_groups).
 
 Concurrent fts_transfer_verify_batch, fts_issue_verify_batch,

@@ -1,5 +1,5 @@
 """GPU: every library knob (FTS_* environment variable read at context creation,
-fts_api.cpp ctx_create) at a non-default value gives the reference's verdicts
+api_ctx.cpp ctx_create) at a non-default value gives the reference's verdicts
 (rp/rangecorrectness.go:141-160) and, where the knob changes the com / x0 code
 path, the same exact intermediates (com, H'_i, x0: ipa.go:200-213).
 

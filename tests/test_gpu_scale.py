@@ -244,7 +244,7 @@ def _raw_timing_names(batch):
 
 
 def test_group_test_round2_exact_verdicts(pp_raw):
-    """the group test's second round (fts_api.cpp
+    """the group test's second round (api_rp.cpp
     rp_group_fallback: failing round-1 groups re-grouped by 8 over the compacted
     survivors) decides which proofs are accepted without their per-proof
     equations.  Forced here (FTS_GT1=64, FTS_GT2_MIN=0) on a coalesced pass of 3
@@ -324,7 +324,7 @@ def test_group_test_round2_exact_verdicts(pp_raw):
 
 
 def test_group_test_adaptive_dense_exact_verdicts(pp_raw):
-    """fts_api.cpp rp_group_fallback, FTS_GT_ADAPT (default on): after a failed
+    """api_rp.cpp rp_group_fallback, FTS_GT_ADAPT (default on): after a failed
     verification whose bad proofs were dense (more than half the batch's proofs
     in failing 256-groups) THAT caller batch starts its next fallback at groups
     of 8 on the small-group kernels, with no second round.  One caller batch of
@@ -473,7 +473,7 @@ def test_dense_and_sparse_batches_in_one_pass(pp_raw):
 
 @pytest.mark.gpu
 def test_idle_burst_splits_into_even_passes(pp_raw):
-    """The dispatcher's idle window (fts_api.cpp fts_rp_batch_verify): 20 batches
+    """The dispatcher's idle window (api_rp.cpp fts_rp_batch_verify): 20 batches
     submitted together on an idle device form two passes of 10 (the first pass
     stops at gather_target = coalesce_max / 2 proofs), whatever the submitter
     threads' timing; every caller keeps its own verdicts."""
@@ -533,7 +533,7 @@ def test_idle_burst_splits_into_even_passes(pp_raw):
 
 @pytest.mark.gpu
 def test_single_fault_locator(pp_raw):
-    """fts_api.cpp rp_locate_single / rp_kernels.hip k_rlc_locate: a failed batch
+    """api_rp.cpp rp_locate_single / rp_kernels.hip k_rlc_locate: a failed batch
     check with ONE bad proof is decided by the index-weighted recombination
     (S' = (i + 1) S) and that proof's per-proof equations, without the group test;
     the other proofs' deferred IPA structural verdicts (a truncated IPA: "invalid

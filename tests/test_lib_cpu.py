@@ -37,6 +37,18 @@ def test_owned_types_check():
     assert "owned_check: ok" in out.stdout
 
 
+def test_action_stage_check():
+    """lib/stage_check (csrc/tools/stage_check.cpp): the host half of action
+    staging (host/action_stage.hpp) on honest, truncated and corrupted proofs,
+    as a plain program built with the host address / undefined-behaviour
+    sanitizers (a report aborts it)"""
+    exe = os.path.join(ROOT, "fabric-token-sdk_amd", "lib", "stage_check")
+    pp = os.path.join(ROOT, "tests", "golden", "zkatdlog_pp.json")
+    out = subprocess.run([exe, pp], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0, out.stdout + out.stderr
+    assert "stage_check: ok" in out.stdout
+
+
 def test_status_strings():
     from fts_gpu import _lib as L
     assert L.status_str(L.FTS_E_RP_INVALID) == "invalid range proof"
@@ -167,7 +179,7 @@ def test_multi_device_context_merges_in_caller_order():
 
 
 def test_action_staging_host_only(host_pp):
-    """fts_api.cpp act_stage on a host-only context (fts_debug_stage_actions): the
+    """host/action_stage.hpp on a host-only context (fts_debug_stage_actions): the
     chunked layout + direct-to-staging decode of transfers and issues, honest and
     malformed (truncated, empty, garbage, 1-in/1-out, nil sigma), more actions than
     one 128-action chunk -- no crash, FTS_API_OK, step timings filled"""

@@ -1,4 +1,4 @@
-"""Host cost of an action call's staging (fts_api.cpp act_stage): DER parse of
+"""Host cost of an action call's staging (host/action_stage.hpp): DER parse of
 N 2-in/2-out transfers straight into the device layout, on a host-only context
 (no GPU; fts_debug_stage_actions).  Usage:
     python tools/host_parse_bench.py [N] [bits] [reps]
