@@ -1,7 +1,8 @@
 // BN254 G1 (y^2 = x^3 + 3) on gfx950: Jacobian coordinates, one point per lane.
 //
 // Formulas (EFD, a = 0): dbl-2009-l (2M+5S), madd-2007-bl (7M+4S),
-// add-2007-bl (11M+5S).  Exceptional cases (identity operands, P == Q,
+// add-2007-bl (11M+5S); the add-only accumulators use extended Jacobian
+// coordinates (G1X below).  Exceptional cases (identity operands, P == Q,
 // P == -Q) are handled with data-dependent branches that are never taken on
 // honest inputs but keep adversarial inputs exact.
 //
@@ -135,6 +136,51 @@ FTS_DEV G1J g1j_add(const G1J& p, const G1J& q) {
   r.x = f_sub(f_sub(fp_sqr(rr), j), f_dbl(v));
   r.y = f_sub(fp_mul(rr, f_sub(v, r.x)), f_dbl(fp_mul(s1, j)));
   r.z = fp_mul(f_sub(f_sub(fp_sqr(f_add(p.z, q.z)), z1z1), z2z2), h);
+  return r;
+}
+
+// ------------------------------------------------- extended Jacobian (XYZZ)
+// x = X / ZZ, y = Y / ZZZ with ZZ^3 = ZZZ^2; identity <=> zz == 0 (then zzz == 0
+// too).  fp_sqr costs a full product here (see above), so the formulas that
+// trade products for squarings buy nothing: madd-2008-s is 8M + 2S = 10 products
+// against the 11 of madd-2007-bl, add-2008-s 12M + 2S = 14 against 16, with half
+// the field additions.  A doubling is 9 against 7, so only the accumulators of
+// kernels that never double (fixed-base sums, MSM bucket chunks) use it; they
+// hand their sum on as a G1J (g1x_to_jac, 2 products).
+struct G1X {
+  Fp x, y, zz, zzz;
+};
+FTS_DEV G1X g1x_identity() {
+  G1X r;
+  r.x = f_one<FpP>();
+  r.y = f_one<FpP>();
+  r.zz = f_zero<FpP>();
+  r.zzz = f_zero<FpP>();
+  return r;
+}
+// (X, Y, ZZ, ZZZ) -> (X ZZ, Y ZZZ, ZZ): Z = ZZ gives Z^2 = ZZ^2, Z^3 = ZZZ^2;
+// the identity (zz == 0) maps to z == 0
+FTS_DEV G1J g1x_to_jac(const G1X& p) {
+  G1J r;
+  r.x = fp_mul(p.x, p.zz);
+  r.y = fp_mul(p.y, p.zzz);
+  r.z = p.zz;
+  return r;
+}
+// dbl-2008-s-1 (6M + 3S); only on the exceptional P == Q branch of the additions.
+// y == 0 (no such point on the curve) gives zz == 0, the identity
+FTS_DEV G1X g1x_dbl(const G1X& p) {
+  Fp u = f_dbl(p.y);
+  Fp v = fp_sqr(u);
+  Fp w = fp_mul(u, v);
+  Fp s = fp_mul(p.x, v);
+  Fp xx = fp_sqr(p.x);
+  Fp m = f_add(f_dbl(xx), xx);
+  G1X r;
+  r.x = f_sub(fp_sqr(m), f_dbl(s));
+  r.y = f_sub(fp_mul(m, f_sub(s, r.x)), fp_mul(w, p.y));
+  r.zz = fp_mul(v, p.zz);
+  r.zzz = fp_mul(w, p.zzz);
   return r;
 }
 

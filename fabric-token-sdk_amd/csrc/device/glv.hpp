@@ -10,7 +10,7 @@
 // (ecc/bn254 G1 ScalarMultiplication); the values here are derived from the
 // curve (tools/glv_constants.py), not copied.
 #pragma once
-#include "fixed_base.hpp"  // madd_inl (includes g1.hpp)
+#include "fixed_base.hpp"  // madd_inl, add_inl (includes g1.hpp)
 
 namespace fts {
 
@@ -124,37 +124,6 @@ FTS_DEV Fp glv_beta() {
 #pragma unroll
   for (int i = 0; i < 8; i++) b.v[i] = Glv::BETA[i];
   return b;
-}
-
-// p += q (both Jacobian): add-2007-bl, inlined (exceptional cases inline too,
-// so the caller's loop never makes an out-of-line call)
-FTS_DEV void add_inl(G1J& p, const G1J& q) {
-  if (f_is_zero(q.z)) return;
-  if (f_is_zero(p.z)) {
-    p = q;
-    return;
-  }
-  Fp z1z1 = fp_sqr(p.z);
-  Fp z2z2 = fp_sqr(q.z);
-  Fp u1 = fp_mul(p.x, z2z2);
-  Fp u2 = fp_mul(q.x, z1z1);
-  Fp s1 = fp_mul(fp_mul(p.y, q.z), z2z2);
-  Fp s2 = fp_mul(fp_mul(q.y, p.z), z1z1);
-  Fp h = f_sub(u2, u1);
-  Fp rr = f_sub(s2, s1);
-  if (f_is_zero(h)) {
-    p = f_is_zero(rr) ? g1j_dbl(p) : g1j_identity();
-    return;
-  }
-  Fp i = fp_sqr(f_dbl(h));
-  Fp j = fp_mul(h, i);
-  rr = f_dbl(rr);
-  Fp v = fp_mul(u1, i);
-  Fp x3 = f_sub(f_sub(fp_sqr(rr), j), f_dbl(v));
-  Fp y3 = f_sub(fp_mul(rr, f_sub(v, x3)), f_dbl(fp_mul(s1, j)));
-  p.z = fp_mul(f_sub(f_sub(fp_sqr(f_add(p.z, q.z)), z1z1), z2z2), h);
-  p.x = x3;
-  p.y = y3;
 }
 
 // Per-lane table of 1..8 * P in global memory, [entry][word][stride] with

@@ -131,7 +131,7 @@ struct BnCurve {
     Scalar s;
 #pragma unroll
     for (int q = 0; q < 8; q++) s.v[q] = k[q];
-    fb_mul_acc(acc, tables + (size_t)base * FB_WORDS_PER_BASE, s);
+    fb_mul_acc_jac(acc, tables + (size_t)base * FB_WORDS_PER_BASE, s);  // Jacobian: k_idv_var's registers
   }
   static FTS_DEV void decompose(const uint32_t k[8], uint32_t k1[4], uint32_t& s1, uint32_t k2[4], uint32_t& s2) {
     glv_decompose<Glv>(k, k1, s1, k2, s2);

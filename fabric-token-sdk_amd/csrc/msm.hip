@@ -480,7 +480,7 @@ __global__ void __launch_bounds__(64, 4) k_msm_chunks(MsmIdx p, const uint32_t* 
   const uint32_t lo = j * (uint32_t)p.ch, hi = min(cnt, lo + (uint32_t)p.ch);
   const uint32_t* S = sorted + offsets[b];
   const Fp beta = glv_beta();
-  G1J acc = g1j_identity();
+  G1X acc = g1x_identity();  // additions only: XYZZ, Jacobian again at the store
   // the next entry's point is gathered while the current addition runs
   // (absent points never get a bucket entry, so msm_src is >= 0 here; a
   // two-deep prefetch measured slower: 2.29 -> 2.36 ms at 2^20 points)
@@ -498,12 +498,12 @@ __global__ void __launch_bounds__(64, 4) k_msm_chunks(MsmIdx p, const uint32_t* 
     if (!g1a_is_identity(q)) {
       if ((e & 0x7fffffffu) >= (uint32_t)N) q.x = fp_mul(q.x, beta);
       if (e >> 31) q.y = f_neg(q.y);
-      madd_inl(acc, q);
+      xmadd_inl(acc, q);
     }
     e = en;
     q = qn;
   }
-  store_g1j(partials + (size_t)g * 24, acc);
+  store_g1j(partials + (size_t)g * 24, g1x_to_jac(acc));
 }
 
 // one lane per bucket: sum of its chunk partials (usually 1..4)
@@ -808,8 +808,10 @@ static void launch_msm_accumulate(const MsmPlan& p, const uint32_t* points, hipS
   FTS_LAUNCH(k_msm_chunks, p.NC, 64, s, msm_idx(p), p.scratch + 2 * (size_t)p.NBLK + 1, p.d_win, points, p.offsets,
              p.counts, p.chunk_off,
              p.chunk_bkt, p.sorted, p.partials);
-  // expected nonzero digits: N * nw * (1 - 2^-c) ~ N * nw mixed additions
-  tl->mark("k_msm_chunks", s, (double)p.NV * p.nw * (COST_MADD + 0.5));
+  // expected nonzero digits: N * nw * (1 - 2^-c) ~ N * nw XYZZ mixed additions (half
+  // of them with the beta product), and one conversion to Jacobian per chunk (the
+  // chunk count is known on the device only: priced as full chunks, a lower bound)
+  tl->mark("k_msm_chunks", s, (double)p.NV * p.nw * (COST_XMADD + 0.5 + COST_X2J / p.ch));
   if (ev_stage && stage == 2) (void)hipEventRecord(ev_stage, s);
   FTS_LAUNCH(k_msm_bucket_sum, p.NB, g_lat_bs, s, p.NB, p.ch, p.counts, p.chunk_off, p.partials, p.buckets);
   tl->mark("k_msm_bucket_sum", s, 0);

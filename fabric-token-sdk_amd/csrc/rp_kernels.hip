@@ -1679,7 +1679,7 @@ void launch_rp_batch(const RpBatchDev& d, const RlcDev& r, const uint32_t* table
                      const uint8_t* x0_const, const uint8_t* x0_tmpl, hipStream_t s, hipStream_t s2, hipStream_t s3,
                      hipStream_t s4, Timeline* tl, int wbits) {
   // fixed-base products over the wide tables: 12 (20-bit) or 11 (22-bit) additions each
-  const double cost_fbw = wbits == 22 ? 11.0 * COST_MADD : COST_FBW_FRESH;
+  const double cost_fbw = wbits == 22 ? 11.0 * COST_XMADD + COST_X2J : COST_FBW_FRESH;
   const int B = d.B, n = d.n, k = d.k, NC = rlc_ncols(n);
   if (!B) return;
   if (d.excl) (void)hipMemsetAsync(d.excl, 0, (size_t)B * 4, s);
@@ -1961,7 +1961,8 @@ void launch_rlc_group_test(const RpBatchDev& d, const RlcDev& r, const uint32_t*
     const int nch = gt_nchunks(n);
     FTS_LAUNCH(k_rlc_group_cols_small, (size_t)G * nch, 256, s, d.B, n, k, G, gs, sel, d.ch, r.coef, d.ypow, d.svec,
                d.zvec, tables, gfix);
-    tl->mark("k_rlc_group_cols", s, (double)G * (gs * 3.0 * n + NC * FB_NW * COST_MADD));
+    // per group: NC fixed-base products; a lane's first one is copied into its accumulator
+    tl->mark("k_rlc_group_cols", s, (double)G * (gs * 3.0 * n + NC * COST_FB_FRESH + (NC - nch) * COST_ADD));
     launch_msm_small(p, d.pts, r.msc, gfix, nch, s, tl);
     FTS_LAUNCH(k_rlc_group_final, (size_t)G * gs, 256, s, G * gs, gs, sel, p.out, d.status, d.ipa_flag, next,
                next_count);
