@@ -283,7 +283,7 @@ FTS_DEV void fb_mul_acc(G1J& acc, const uint32_t* __restrict__ table, const Scal
 // acc += k * B over a 16-bit window table with every entry added straight into
 // the Jacobian accumulator (madd_inl, 11 products per window): for a kernel whose
 // register budget has no room for the XYZZ sum beside its accumulator
-// (idemix_identity.hip k_idv_var: 155 -> 179 VGPRs, 3 -> 2 waves per SIMD with it)
+// (idv_kernels.hpp k_idv_var: 155 -> 179 VGPRs, 3 -> 2 waves per SIMD with it)
 FTS_DEV void fb_mul_acc_jac(G1J& acc, const uint32_t* __restrict__ table, const Scalar& k) {
   uint32_t s[8];
 #pragma unroll

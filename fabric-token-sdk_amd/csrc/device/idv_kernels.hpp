@@ -22,57 +22,33 @@
 //                  lines of W and g2, multi-Miller loop, final exponentiation)
 // Curves: BN254 (gnark; G1 64-byte raw encodings, 16-bit signed fixed-base
 // tables) and FP256BN (AMCL; 0x04 || X || Y, 16-bit unsigned tables), behind a
-// traits struct each.
+// traits struct each.  Kernels, device tables and the launch_*<CV> templates only:
+// idemix_identity_bn.hip and idemix_identity_fbn.hip instantiate one curve each
+// (a curve's pairing kernels are minutes of device compilation; the two units
+// build in parallel), and the host code (api_idemix.cpp) sees device/launch.hpp.
+#pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <string.h>
-#include <sys/random.h>
 
-#include <algorithm>
-#include <atomic>
-#include <functional>
-#include <memory>
-#include <mutex>
-#include <string>
 #include <type_traits>
-#include <unordered_map>
-#include <vector>
 
-#include "../../include/fts_gpu.h"
-#include "common/chacha20.hpp"
-#include "common/sha256.hpp"
-#include "device/fixed_base.hpp"
-#include "device/glv.hpp"
-#include "device/helpers.hpp"
-#include "device/transcript.hpp"
-#include "device/fp256bn.hpp"
-#include "device/pairing.hpp"
-#include "device/launch.hpp"
-#include "host/bn254_host.hpp"
-#include "host/hip_owned.hpp"
-#include "host/host_pool.hpp"
-#include "host/pb.hpp"
+#include "../../../include/fts_gpu.h"
+#include "../common/chacha20.hpp"
+#include "../common/sha256.hpp"
+#include "fixed_base.hpp"
+#include "glv.hpp"
+#include "helpers.hpp"
+#include "transcript.hpp"
+#include "fp256bn.hpp"
+#include "pairing.hpp"
+#include "launch.hpp"
+#include "../host/idemix_parse.hpp"  // the record layout (NPT, P_*, R_*, F_*, ...)
 
 namespace idv {
 
 using namespace fts;
 
 // ------------------------------------------------------------- constants
-// bases of the issuer tables: HSk, HRand, HAttrs[0..3], g1
-constexpr int NB = 7, B_HSK = 0, B_HRAND = 1, B_HA = 2, B_G1 = 6;
-constexpr int NPT = 7;   // raw points per item: nymPK, A', ABar, B', Nym, EidNym, RhNym
-constexpr int P_NYMPK = 0, P_AP = 1, P_ABAR = 2, P_BP = 3, P_NYM = 4, P_EID = 5, P_RH = 6;
-constexpr int NVAR = 6;  // variable-base products: A' sE, D (-c), B' sR3, Nym (-c), EidNym (-c), RhNym (-c)
-constexpr int NFIX = 11;  // distinct fixed-base products (three serve two t-values each)
-constexpr int NSC = NVAR + NFIX;
-// record words: flags, c (raw LE limbs, compared), nonce (BE words, hashed), scalars
-constexpr int R_FLAGS = 0, R_C = 1, R_NONCE = 9, R_SC = 17;
-constexpr int REC_WORDS = R_SC + NSC * 8;  // 153
-constexpr int REC_STRIDE = 156;            // 16-byte aligned records
-static_assert(REC_STRIDE >= REC_WORDS && REC_STRIDE % 4 == 0, "record stride");
-// flags (host parse), in the reference's order of checks
-constexpr uint32_t F_EARLY_MALFORMED = 1u, F_NO_EID = 2u, F_NO_RH = 4u, F_LATE_MALFORMED = 8u, F_REVOCATION = 16u,
-                   F_C_BIG = 32u;
 // targets: t1..t5 = 0..4
 __device__ constexpr int VAR_PT[NVAR] = {P_AP, -1, P_BP, P_NYM, P_EID, P_RH};  // -1: D = ABar - B'
 __device__ constexpr int VAR_T[NVAR] = {0, 0, 1, 2, 3, 4};
@@ -88,7 +64,6 @@ __device__ constexpr int FIX_T2[NFIX] = {-1, -1, 2, -1, -1, 3, 4, -1, -1, -1, -1
 // transcript: label || t1 t2 t3 A' ABar B' Nym EidNym t4 RhNym t5 || ipk.Hash || Disclosure (4 zero bytes)
 constexpr char LABEL[] = "signWithEidNymRhNym";
 constexpr int LABEL_LEN = 19;
-constexpr int MSG_MAX = 832;  // 13 SHA-256 blocks (FP256BN: 19 + 11 * 65 + 36 = 770 bytes)
 
 // ----------------------------------------------------------- curve traits
 // BN254 (gnark-crypto through mathlib): G1.Bytes() = 64-byte raw X || Y, 64 zero
@@ -460,25 +435,6 @@ FTS_DEV bool g2_in_subgroup_bn(const pair::F2<pair::BnField>& qx, const pair::F2
   return eq(acc.x, mul(qx, z2)) && eq(acc.y, neg(mul(qy, z3)));
 }
 
-#ifndef IDV_FBN_TU  // BN254 only: compiled in the main translation unit
-// U distinct epoch keys (128 raw bytes each, BN254): ok[u] <- the key decodes (on the
-// twist, canonical) and lies in the subgroup (the identity does)
-// lane j checks distinct key idx[j] (the keys the context has not checked before)
-__global__ void __launch_bounds__(64) k_idv_g2_check(int M, const int32_t* __restrict__ idx,
-                                                     const uint8_t* __restrict__ keys, int32_t* __restrict__ ok) {
-  const int j = blockIdx.x * blockDim.x + threadIdx.x;
-  if (j >= M) return;
-  const int u = idx[j];
-  pair::F2<pair::BnField> x, y;
-  const uint8_t* kr = keys + (size_t)u * 128;
-  bool good = decode_g2<BnCurve>(kr, x, y);
-  bool zero = true;
-  for (int q = 0; q < 128; q++) zero = zero && kr[q] == 0;
-  if (good && !zero) good = g2_in_subgroup_bn(x, y);
-  ok[u] = good ? 1 : 0;
-}
-#endif
-
 // ----------------------------------------------------------------- kernels
 // lines of W (lane 0) and g2 (lane 1); wraw: W as 128 raw bytes; ok[0] <- W valid
 template <class CV>
@@ -518,7 +474,6 @@ FTS_DEV size_t sc_dp(size_t n) { return (size_t)5 * 24 * n; }
 FTS_DEV size_t sc_idm(size_t n) { return sc_dp(n) + (size_t)NPT * 16 * n; }
 FTS_DEV size_t sc_vr(size_t n) { return sc_idm(n) + ((n + 3) & ~size_t(3)); }  // keeps sc_tv 16-byte aligned (GTab rows)
 FTS_DEV size_t sc_tv(size_t n) { return sc_vr(n) + (size_t)NSC * 24 * n; }
-inline size_t idv_scratch_words(size_t n) { return (5 * 24 + NPT * 16 + 1 + NSC * 24 + NVAR * AT_WORDS) * n + 3; }
 
 // Three kernels per batch (round 4; one lane per identity for everything left
 // 1,024 waves at one per SIMD, 30 % of the MAD peak):
@@ -800,20 +755,8 @@ __global__ void __launch_bounds__(64, FTS_IDV_OCC) k_idv_pairing(int n, const ui
 // its identities paired one by one (k_idv_pairing over the k_idv_bp_sel list), so
 // every verdict is the per-identity one.  Work per identity: two 64-bit GLV chains
 // (17 windows) instead of a 2-pairing Miller loop and a final exponentiation.
-constexpr int BP_G = 256;  // identities per group = threads of a k_idv_bp_terms block
-struct Key8 {
-  uint32_t k[8];
-};
-// scratch (the t-value kernels' scratch, free by then):
-//   lane tables [2][AT_WORDS][n] | group sums [ng][2][24] | gok [ng] | count | list [n]
-inline size_t bp_part_off(size_t n) { return (size_t)2 * AT_WORDS * n; }
-inline size_t bp_gok_off(size_t n, size_t ng) { return bp_part_off(n) + ng * 48; }
-inline size_t bp_cnt_off(size_t n, size_t ng) { return bp_gok_off(n, ng) + ng; }
-inline size_t bp_list_off(size_t n, size_t ng) { return bp_cnt_off(n, ng) + 64; }
-inline size_t bp_scratch_words(size_t n) {
-  const size_t ng = (n + BP_G - 1) / BP_G;
-  return bp_list_off(n, ng) + n;
-}
+// BP_G identities per group = threads of a k_idv_bp_terms block; its scratch layout
+// (bp_*_off) is with the other size functions in idemix_identity_bn.hip.
 
 // block = group g, blockIdx.y = which point (0: A', 1: -ABar): rho_i * P_i summed
 // over the group's identities still OK (the others contribute O), LDS tree
@@ -942,22 +885,8 @@ __global__ void __launch_bounds__(64) k_idv_pairing_debug(const uint32_t* __rest
 }
 
 // ------------------------------------------------- per-curve launch sequences
-// Instantiated once per curve and translation unit: BN254 here, FP256BN in
-// idemix_identity_fbn.hip (each curve's pairing kernels are minutes of device
-// compilation; two units build in parallel).
-struct Chain {
-  hipStream_t s;
-  int n;
-  const uint32_t* rec;
-  const uint8_t *pts, *epk;
-  uint32_t *scr, *pin;
-  int32_t *zk, *st;
-  const int32_t *eidx, *g2ok;  // BN254 epoch keys (FP256BN: null)
-  const uint32_t *tables, *hash, *lines;
-  uint8_t* msg;
-  int32_t *gok, *cnt, *list;
-  Key8 key;
-};
+// Declared in device/launch.hpp (with Chain); instantiated once per curve, each in
+// its own translation unit.
 // decode, the t-value products, the t-values and the transcript
 template <class CV>
 void launch_tvals(const Chain& c) {
@@ -986,661 +915,4 @@ void launch_lines(const uint8_t* w, uint32_t* lines, int32_t* ok, hipStream_t s)
   k_idv_lines<CV><<<1, 64, 0, s>>>(w, lines, ok);
 }
 
-#ifdef IDV_FBN_TU
-}  // namespace idv (the FP256BN unit holds kernels only)
-#else  // the host side
-extern template void launch_tvals<FbnCurve>(const Chain&);
-extern template void launch_batch<FbnCurve>(const Chain&);
-extern template void launch_pairing<FbnCurve>(const Chain&, unsigned, bool);
-extern template void launch_lines<FbnCurve>(const uint8_t*, uint32_t*, int32_t*, hipStream_t);
-
-// ------------------------------------------------------------------- host
-const uint32_t kRbn[8] = {0xf0000001u, 0x43e1f593u, 0x79b97091u, 0x2833e848u,
-                          0x8181585du, 0xb85045b6u, 0xe131a029u, 0x30644e72u};
-const uint32_t kRfbn[8] = {0xd10b500du, 0xf62d536cu, 0x1299921au, 0x0cdc65fbu,
-                           0xee71a49eu, 0x46e5f25eu, 0xfffcf0cdu, 0xffffffffu};
-
-bool ge(const uint32_t a[8], const uint32_t m[8]) {
-  for (int k = 7; k >= 0; k--)
-    if (a[k] != m[k]) return a[k] > m[k];
-  return true;
-}
-void subm(uint32_t a[8], const uint32_t m[8]) {
-  uint64_t bw = 0;
-  for (int k = 0; k < 8; k++) {
-    const uint64_t d = (uint64_t)a[k] - m[k] - bw;
-    a[k] = (uint32_t)d;
-    bw = (d >> 63) & 1;
-  }
-}
-// big-endian bytes -> LE limbs if the value fits 256 bits
-bool be_limbs(const uint8_t* b, size_t len, uint32_t out[8]) {
-  size_t st = 0;
-  while (st < len && b[st] == 0) st++;
-  memset(out, 0, 32);
-  if (len - st > 32) return false;
-  for (size_t k = st; k < len; k++) {
-    const size_t bit = (len - 1 - k) * 8;
-    out[bit / 32] |= (uint32_t)b[k] << (bit % 32);
-  }
-  return true;
-}
-// (x * 256 + byte) mod m for x < m < 2^256
-void mulacc_byte(uint32_t x[8], uint8_t byte, const uint32_t m[8]) {
-  uint32_t t[9];
-  uint64_t c = byte;
-  for (int k = 0; k < 8; k++) {
-    const uint64_t v = ((uint64_t)x[k] << 8) + c;
-    t[k] = (uint32_t)v;
-    c = v >> 32;
-  }
-  t[8] = (uint32_t)c;
-  for (int guard = 0; guard < 600; guard++) {
-    if (t[8] == 0 && !ge(t, m)) break;
-    uint64_t bw = 0;
-    for (int k = 0; k < 9; k++) {
-      const uint64_t d = (uint64_t)t[k] - (k < 8 ? m[k] : 0u) - bw;
-      t[k] = (uint32_t)d;
-      bw = (d >> 63) & 1;
-    }
-  }
-  memcpy(x, t, 32);
-}
-void mod_m(const uint8_t* b, size_t len, const uint32_t m[8], uint32_t out[8]) {
-  if (be_limbs(b, len, out)) {
-    while (ge(out, m)) subm(out, m);
-    return;
-  }
-  memset(out, 0, 32);
-  for (size_t k = 0; k < len; k++) mulacc_byte(out, b[k], m);
-}
-
-struct Span {
-  const uint8_t* p = nullptr;
-  size_t n = 0;
-  bool set = false;
-};
-// ECP{1 x, 2 y} -> 64 raw bytes; false if a coordinate is not 32 bytes or the message is malformed
-bool ecp_raw(const Span& s, uint8_t out[64]) {
-  if (!s.set) return false;
-  Pb pb{s.p, s.n};
-  Span f[3];
-  while (pb.o < pb.n) {
-    uint32_t fn, wt;
-    const uint8_t* v;
-    size_t vl;
-    uint64_t iv;
-    if (!pb.next(fn, wt, v, vl, iv)) return false;
-    if (fn == 1 || fn == 2) {
-      if (wt != 2) return false;
-      f[fn].p = v, f[fn].n = vl, f[fn].set = true;
-    }
-  }
-  if (f[1].n != 32 || f[2].n != 32) return false;
-  memcpy(out, f[1].p, 32);
-  memcpy(out + 32, f[2].p, 32);
-  return true;
-}
-bool ecp2_raw(const Span& s, uint8_t out[128]) {
-  if (!s.set) return false;
-  Pb pb{s.p, s.n};
-  Span f[5];
-  while (pb.o < pb.n) {
-    uint32_t fn, wt;
-    const uint8_t* v;
-    size_t vl;
-    uint64_t iv;
-    if (!pb.next(fn, wt, v, vl, iv)) return false;
-    if (fn >= 1 && fn <= 4) {
-      if (wt != 2) return false;
-      f[fn].p = v, f[fn].n = vl, f[fn].set = true;
-    }
-  }
-  for (int q = 1; q <= 4; q++) {
-    if (f[q].n != 32) return false;
-    memcpy(out + 32 * (q - 1), f[q].p, 32);
-  }
-  return true;
-}
-
-// SerializedIdemixIdentity + its Signature proto -> record, raw points, epoch key;
-// returns the identity-level status (FTS_OK: to the device)
-int32_t parse_identity(const uint8_t* id, size_t len, bool bn, const uint32_t* rmod, uint32_t* rec, uint8_t* pts,
-                       uint8_t* epk) {
-  memset(rec, 0, REC_STRIDE * 4);
-  memset(pts, 0, NPT * 64);
-  memset(epk, 0, 128);
-  if (!id || !len) return FTS_E_ID_MALFORMED;  // "empty identity"
-  Span nym, proof;
-  {
-    Pb pb{id, len};
-    while (pb.o < pb.n) {
-      uint32_t f, wt;
-      const uint8_t* v;
-      size_t vl;
-      uint64_t iv;
-      if (!pb.next(f, wt, v, vl, iv)) return FTS_E_ID_MALFORMED;
-      if (f >= 1 && f <= 4 && wt != 2) return FTS_E_ID_MALFORMED;
-      if (f == 1) nym.p = v, nym.n = vl, nym.set = true;
-      if (f == 4) proof.p = v, proof.n = vl, proof.set = true;
-    }
-  }
-  if (nym.n == 0) return FTS_E_ID_MALFORMED;  // "pseudonym's public key is empty"
-  // KeyImport: G1.Bytes() form; its point checks run on the device
-  if (bn ? nym.n != 64 : (nym.n != 65 || nym.p[0] != 0x04)) return FTS_E_ID_BADNYM;
-  memcpy(pts + P_NYMPK * 64, nym.p + (bn ? 0 : 1), 64);
-  uint32_t& flags = rec[R_FLAGS];
-  // Signature proto (IBM/idemix idemix.proto, restated): 1 a_prime 2 a_bar 3 b_prime (ECP),
-  // 4 c 5 s_sk 6 s_e 7 s_r2 8 s_r3 9 s_s_prime, 10 s_attrs (repeated), 11 nonce, 12 nym (ECP),
-  // 13 s_r_nym, 14 revocation_epoch_pk (ECP2), 15 revocation_pk_sig, 16 epoch, 17 non_revocation_proof,
-  // 18 eid_nym {1 nym, 2 s_eid}, 19 rh_nym {1 nym, 2 s_rh}
-  Span f[20];
-  std::vector<Span> attrs;
-  attrs.reserve(4);
-  if (proof.n == 0) {
-    flags |= F_EARLY_MALFORMED;  // an empty signature is rejected before Unmarshal
-  } else {
-    Pb pb{proof.p, proof.n};
-    while (pb.o < pb.n) {
-      uint32_t fn, wt;
-      const uint8_t* v;
-      size_t vl;
-      uint64_t iv;
-      if (!pb.next(fn, wt, v, vl, iv)) {
-        flags |= F_EARLY_MALFORMED;
-        break;
-      }
-      if (fn >= 1 && fn <= 19 && fn != 16 && wt != 2) {
-        flags |= F_EARLY_MALFORMED;
-        break;
-      }
-      if (fn == 16 && wt != 0) {
-        flags |= F_EARLY_MALFORMED;
-        break;
-      }
-      if (fn == 10) attrs.push_back(Span{v, vl, true});
-      else if (fn >= 1 && fn <= 19) f[fn] = Span{v, vl, true};
-    }
-  }
-  // Zr fields: BN254 big-endian integers of any length; FP256BN AMCL FromBytes reads
-  // exactly 32 bytes (a shorter field panics in the reference)
-  auto zr = [&](const Span& s, uint32_t out[8], bool& wide) -> bool {
-    wide = false;
-    if (bn) {
-      uint32_t raw[8];
-      if (!be_limbs(s.p, s.n, raw)) wide = true;
-      mod_m(s.p, s.n, rmod, out);
-      return true;
-    }
-    if (s.n < 32) return false;
-    be_limbs(s.p, 32, out);
-    if (ge(out, rmod)) subm(out, rmod);
-    return true;
-  };
-  uint32_t sc[24][8];
-  memset(sc, 0, sizeof sc);
-  Span eid_nym, rh_nym, s_eid, s_rh;
-  uint32_t rev_alg = 0;
-  if (!(flags & F_EARLY_MALFORMED)) {
-    // sub-messages: 17 NonRevocationProof{1 revocation_alg}, 18 / 19 {1 nym, 2 s}
-    auto sub = [&](const Span& s, Span& a, Span& b) -> bool {
-      if (!s.set) return true;
-      Pb pb{s.p, s.n};
-      while (pb.o < pb.n) {
-        uint32_t fn, wt;
-        const uint8_t* v;
-        size_t vl;
-        uint64_t iv;
-        if (!pb.next(fn, wt, v, vl, iv)) return false;
-        if ((fn == 1 || fn == 2) && wt != 2) return false;
-        if (fn == 1) a = Span{v, vl, true};
-        if (fn == 2) b = Span{v, vl, true};
-      }
-      return true;
-    };
-    bool good = sub(f[18], eid_nym, s_eid) && sub(f[19], rh_nym, s_rh);
-    if (f[17].set) {
-      Pb pb{f[17].p, f[17].n};
-      while (good && pb.o < pb.n) {
-        uint32_t fn, wt;
-        const uint8_t* v;
-        size_t vl;
-        uint64_t iv;
-        if (!pb.next(fn, wt, v, vl, iv)) good = false;
-        else if (fn == 1 && wt != 0) good = false;
-        else if (fn == 1) rev_alg = (uint32_t)iv;
-        else if (fn == 2 && wt != 2) good = false;
-      }
-    }
-    // the scalars: c(4) sSk(5) sE(6) sR2(7) sR3(8) sS'(9) nonce(11) sRNym(13) sAttrs sEid sRh
-    const int fld[8] = {4, 5, 6, 7, 8, 9, 11, 13};
-    bool wide[8] = {false};
-    for (int q = 0; q < 8 && good; q++) good = zr(f[fld[q]], sc[q], wide[q]);
-    for (size_t a = 0; a < attrs.size() && a < 4 && good; a++) {
-      bool w;
-      good = zr(attrs[a], sc[8 + a], w);
-    }
-    for (size_t a = 4; a < attrs.size() && good; a++) {
-      uint32_t tmp[8];
-      bool w;
-      good = zr(attrs[a], tmp, w);
-    }
-    if (good && f[18].set) {
-      bool w;
-      good = zr(s_eid, sc[12], w);
-    }
-    if (good && f[19].set) {
-      bool w;
-      good = zr(s_rh, sc[13], w);
-    }
-    if (!good) {
-      flags |= F_EARLY_MALFORMED;
-    } else {
-      // nonce: Zr.Bytes() of a value wider than 32 bytes panics (mathlib BigToBytes)
-      uint32_t nonce[8];
-      if (bn) {
-        if (!be_limbs(f[11].p, f[11].n, nonce)) flags |= F_EARLY_MALFORMED;
-      } else {
-        be_limbs(f[11].p, 32, nonce);
-      }
-      for (int k = 0; k < 8; k++) rec[R_NONCE + k] = nonce[7 - k];
-      // c: compared as an integer with the recomputed (reduced) challenge
-      uint32_t craw[8];
-      if (bn) {
-        if (!be_limbs(f[4].p, f[4].n, craw) || ge(craw, rmod)) flags |= F_C_BIG;
-      } else {
-        be_limbs(f[4].p, 32, craw);
-        if (ge(craw, rmod)) flags |= F_C_BIG;
-      }
-      memcpy(rec + R_C, craw, 32);
-    }
-  }
-  if (!(flags & F_EARLY_MALFORMED)) {
-    if (!f[18].set) flags |= F_NO_EID;
-    else if (!f[19].set) flags |= F_NO_RH;
-  }
-  if (!(flags & (F_EARLY_MALFORMED | F_NO_EID | F_NO_RH))) {
-    bool good = ecp_raw(f[1], pts + P_AP * 64) && ecp_raw(f[2], pts + P_ABAR * 64) &&
-                ecp_raw(f[3], pts + P_BP * 64) && ecp_raw(f[12], pts + P_NYM * 64) &&
-                ecp_raw(eid_nym, pts + P_EID * 64) && ecp_raw(rh_nym, pts + P_RH * 64) && attrs.size() == 4 &&
-                ecp2_raw(f[14], epk);
-    if (!good) flags |= F_LATE_MALFORMED;
-    if (rev_alg != 0) flags |= F_REVOCATION;
-    // scalars: var [sE, -c, sR3, -c, -c, -c]; fixed as FIX_B / FIX_T
-    uint32_t cm[8], nc[8];
-    memcpy(cm, sc[0], 32);
-    memset(nc, 0, 32);
-    {
-      uint32_t z = 0;
-      for (int k = 0; k < 8; k++) z |= cm[k];
-      if (z) {
-        uint64_t bw = 0;
-        for (int k = 0; k < 8; k++) {
-          const uint64_t d = (uint64_t)rmod[k] - cm[k] - bw;
-          nc[k] = (uint32_t)d;
-          bw = (d >> 63) & 1;
-        }
-      }
-    }
-    const uint32_t* var[NVAR] = {sc[2], nc, sc[4], nc, nc, nc};
-    // fixed: sR2, sS', sSk (t2, t3), sA0, sA1, sA2 (t2, t4), sA3 (t2, t5), c, sRNym, sEid, sRh
-    const uint32_t* fix[NFIX] = {sc[3], sc[5], sc[1], sc[8], sc[9], sc[10], sc[11], cm, sc[7], sc[12], sc[13]};
-    for (int v = 0; v < NVAR; v++) memcpy(rec + R_SC + v * 8, var[v], 32);
-    for (int q = 0; q < NFIX; q++) memcpy(rec + R_SC + (NVAR + q) * 8, fix[q], 32);
-  }
-  return FTS_OK;
-}
-
-#define ICHK(x)                                    \
-  do {                                             \
-    if ((x) != hipSuccess) return FTS_API_EDEVICE; \
-  } while (0)
-
-constexpr int NSLOT = 8;  // calls in flight per handle (each slot: its own stream and buffers, grown on first use;
-                          // 12 concurrent calls hit HSA_STATUS_ERROR_OUT_OF_RESOURCES dispatching the
-                          // scratch-using pairing kernels, gpurun_out/ns)
-struct Slot {
-  Stream stream;
-  DevBuf d_buf;
-  PinBuf h_buf;
-  Event ev[3];
-  float ms[2] = {0.f, 0.f};
-  uint32_t stats[2] = {0u, 0u};
-};
-
 }  // namespace idv
-
-struct fts_idemix_idv {
-  int device = -1;
-  int curve = 1;
-  fts::DevBuf d_tables;  // HSk, HRand, HAttrs[0..3], g1
-  fts::DevBuf d_lines;   // lines of W, then of g2
-  fts::DevBuf d_hash;    // ipk.Hash as 8 big-endian words
-  fts::SlotRing<idv::Slot, idv::NSLOT> ring;  // its lock also guards last_* and g2_seen
-  float last_ms[2] = {0.f, 0.f};
-  // batch pairing check (k_idv_bp_*; FTS_IDV_BATCH=0 pairs every identity, the A/B
-  // and pre-round-6 path); last call's groups and identities paired one by one
-  bool batch = true;
-  uint32_t last_stats[2] = {0u, 0u};
-  // BN254 epoch keys already subgroup-checked by this context (128 raw bytes ->
-  // verdict): an honest stream carries one key per epoch, and k_idv_g2_check is
-  // one 254-step G2 chain on one lane (7.7 ms, on the call's critical path)
-  std::unordered_map<std::string, int32_t> g2_seen;
-  ~fts_idemix_idv() {
-    if (device >= 0) (void)hipSetDevice(device);
-  }
-};
-
-namespace idv {
-int nlines(bool bn) { return bn ? pair::n_lines<pairc::Bn254>() : pair::n_lines<pairc::Fp256bn>(); }
-}  // namespace idv
-
-extern "C" {
-
-int fts_idemix_idv_create(int device, const uint8_t* ipk, size_t ipk_len, int curve_id, fts_idemix_idv** out) {
-  using namespace idv;
-  if (!out || !ipk || !ipk_len || (curve_id != FTS_CURVE_BN254 && curve_id != FTS_CURVE_FP256BN_AMCL))
-    return FTS_API_EINVAL;
-  *out = nullptr;
-  const bool bn = curve_id == FTS_CURVE_BN254;
-  // IssuerPublicKey: 2 h_sk, 3 h_rand, 4 h_attrs (repeated ECP), 5 w (ECP2), 10 hash
-  Pb pb{ipk, ipk_len};
-  Span hsk, hr, w, hash;
-  std::vector<Span> ha;
-  while (pb.o < pb.n) {
-    uint32_t f, wt;
-    const uint8_t* v;
-    size_t vl;
-    uint64_t iv;
-    if (!pb.next(f, wt, v, vl, iv)) return FTS_API_EPP;
-    if (wt != 2) continue;
-    if (f == 2) hsk = Span{v, vl, true};
-    if (f == 3) hr = Span{v, vl, true};
-    if (f == 4) ha.push_back(Span{v, vl, true});
-    if (f == 5) w = Span{v, vl, true};
-    if (f == 10) hash = Span{v, vl, true};
-  }
-  if (ha.size() != 4) return FTS_API_EPP;  // OU, Role, EnrollmentID, RevocationHandle
-  uint8_t raw[NB][64], wraw[128];
-  if (!ecp_raw(hsk, raw[B_HSK]) || !ecp_raw(hr, raw[B_HRAND]) || !ecp2_raw(w, wraw)) return FTS_API_EPP;
-  for (int a = 0; a < 4; a++)
-    if (!ecp_raw(ha[a], raw[B_HA + a])) return FTS_API_EPP;
-  memset(raw[B_G1], 0, 64);  // g1 = (1, 2) on both curves
-  raw[B_G1][31] = 1, raw[B_G1][63] = 2;
-  uint32_t bases[NB * 16];  // BN254: Montgomery (host decode); FP256BN: plain LE limbs
-  for (int b = 0; b < NB; b++) {
-    if (bn) {
-      host::G1A a;
-      if (!host::g1_from_bytes(raw[b], 64, a) || a.inf) return FTS_API_EPP;
-      memcpy(&bases[b * 16], a.x.v, 32);
-      memcpy(&bases[b * 16 + 8], a.y.v, 32);
-    } else {
-      be_limbs(raw[b], 32, &bases[b * 16]);
-      be_limbs(raw[b] + 32, 32, &bases[b * 16 + 8]);
-    }
-  }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return FTS_API_EDEVICE;
-  std::unique_ptr<fts_idemix_idv> k(new fts_idemix_idv());
-  k->device = device;
-  k->curve = curve_id;
-  if (const char* e = getenv("FTS_IDV_BATCH")) k->batch = atoi(e) != 0;
-  if (hipSetDevice(device) != hipSuccess) return FTS_API_EDEVICE;
-  uint32_t hw[8] = {0};
-  {
-    uint8_t h[32] = {0};
-    if (hash.set) memcpy(h, hash.p, std::min<size_t>(hash.n, 32));
-    for (int q = 0; q < 8; q++)
-      hw[q] = ((uint32_t)h[4 * q] << 24) | ((uint32_t)h[4 * q + 1] << 16) | ((uint32_t)h[4 * q + 2] << 8) | h[4 * q + 3];
-  }
-  const size_t wpb = bn ? fb_words_per_base() : fbn_words_per_base();
-  const size_t nl = (size_t)nlines(bn) * pair::LINE_WORDS;
-  Stream s0;
-  DevBuf bases_buf, scr_buf, w_buf, ok_buf;
-  const size_t scr_b = bn ? table_build_scratch_bytes(NB) : (size_t)NB * 16 * 4;
-  bool ok = s0.create() == hipSuccess && k->d_tables.reserve((size_t)NB * wpb * 4) &&
-            k->d_lines.reserve(2 * nl * 4) && k->d_hash.reserve(32) && bases_buf.reserve(sizeof bases) &&
-            scr_buf.reserve(scr_b) && w_buf.reserve(128) && ok_buf.reserve(64);
-  uint32_t* const d_tables = k->d_tables.as<uint32_t>();
-  uint32_t* const d_lines = k->d_lines.as<uint32_t>();
-  uint32_t *const d_bases = bases_buf.as<uint32_t>(), *const d_scr = scr_buf.as<uint32_t>();
-  uint8_t* const d_w = w_buf.as<uint8_t>();
-  int32_t* const d_ok = ok_buf.as<int32_t>();
-  ok = ok && hipMemcpyAsync(d_bases, bases, sizeof bases, hipMemcpyHostToDevice, s0) == hipSuccess &&
-       hipMemcpyAsync(d_w, wraw, 128, hipMemcpyHostToDevice, s0) == hipSuccess &&
-       hipMemcpyAsync(k->d_hash.p, hw, 32, hipMemcpyHostToDevice, s0) == hipSuccess &&
-       hipMemsetAsync(d_ok, 0, 64, s0) == hipSuccess;
-  int32_t hok[NB + 1] = {0};
-  if (ok) {
-    if (bn) {
-      launch_build_tables(d_bases, NB, d_tables, d_scr, s0);
-      launch_lines<BnCurve>(d_w, d_lines, d_ok + NB, s0);
-    } else {
-      fbn_build_tables(d_bases, NB, d_scr, d_ok, d_tables, s0);
-      launch_lines<FbnCurve>(d_w, d_lines, d_ok + NB, s0);
-    }
-    ok = hipGetLastError() == hipSuccess &&
-         hipMemcpyAsync(hok, d_ok, sizeof hok, hipMemcpyDeviceToHost, s0) == hipSuccess &&
-         hipStreamSynchronize(s0) == hipSuccess;
-  }
-  if (s0) (void)hipStreamSynchronize(s0);  // an error path may leave copies queued on s0
-  if (!ok) return FTS_API_EDEVICE;
-  bool valid = hok[NB] == 1;  // W on the twist
-  if (!bn)
-    for (int b = 0; b < NB; b++) valid = valid && hok[b] == 1;
-  if (!valid) return FTS_API_EPP;
-  for (auto& S : k->ring.slot) {
-    ok = ok && S.stream.create() == hipSuccess;
-    for (auto& e : S.ev) ok = ok && e.create() == hipSuccess;
-  }
-  if (!ok) return FTS_API_EDEVICE;
-  *out = k.release();
-  return FTS_API_OK;
-}
-
-void fts_idemix_idv_destroy(fts_idemix_idv* k) { delete k; }
-
-int fts_idemix_identity_verify_batch(fts_idemix_idv* K, size_t n, const uint8_t* const* ids, const size_t* id_len,
-                                     int32_t* status) {
-  using namespace idv;
-  if (!K || n > (size_t)(1u << 22) || (n && (!ids || !id_len || !status))) return FTS_API_EINVAL;
-  if (n == 0) return FTS_API_OK;
-  const bool bn = K->curve == FTS_CURVE_BN254;
-  auto guard = K->ring.acquire([K](Slot& S) {
-    K->last_ms[0] = S.ms[0], K->last_ms[1] = S.ms[1];
-    K->last_stats[0] = S.stats[0], K->last_stats[1] = S.stats[1];
-  });
-  Slot& D = guard.slot();
-  ICHK(hipSetDevice(K->device));
-  // staged (host + device): rec | pts | epk | status | eidx | distinct epoch keys (BN254);
-  // device only: zk | pin | scratch | msg | g2ok
-  const size_t rec_b = n * REC_STRIDE * 4, pts_b = n * NPT * 64, epk_b = n * 128, st_b = n * 4;
-  const size_t o_pts = rec_b, o_epk = o_pts + pts_b, o_st = o_epk + epk_b, o_eidx = o_st + st_b,
-               o_uk = o_eidx + n * 4;
-  // host only: the distinct keys' verdicts (cached or read back) and the indices to check
-  const size_t o_gk = (o_uk + epk_b + 255) & ~size_t(255), o_miss = o_gk + n * 4;
-  const size_t o_cnt = o_miss + n * 4;  // the batch check's list length, read back
-  const size_t h_need = (o_cnt + 4 + 255) & ~size_t(255);
-  const size_t o_zk = h_need, o_pin = (o_zk + n * 4 + 255) & ~size_t(255), o_scr = o_pin + n * 32 * 4;
-  const size_t scr_w = std::max(idv_scratch_words(n), bp_scratch_words(n));
-  const size_t o_msg = (o_scr + scr_w * 4 + 255) & ~size_t(255);
-  const size_t o_g2ok = (o_msg + (size_t)MSG_MAX * n + 255) & ~size_t(255);
-  const size_t d_need = o_g2ok + 2 * n * 4;  // U verdicts, then the M key indices to check
-  if (D.h_buf.cap < h_need && !D.h_buf.reserve(h_need + h_need / 2)) return FTS_API_ENOMEM;
-  if (D.d_buf.cap < d_need && !D.d_buf.reserve(d_need + d_need / 2)) return FTS_API_ENOMEM;
-  uint8_t* h = D.h_buf.as<uint8_t>();
-  const uint32_t* rmod = bn ? kRbn : kRfbn;
-  const size_t CH = 1024, nch = (n + CH - 1) / CH;
-  host_parallel_for(nch, [&](size_t c) {
-    for (size_t i = c * CH; i < std::min(n, (c + 1) * CH); i++)
-      reinterpret_cast<int32_t*>(h + o_st)[i] =
-          parse_identity(ids[i], id_len[i], bn, rmod, reinterpret_cast<uint32_t*>(h) + i * REC_STRIDE,
-                         h + o_pts + i * NPT * 64, h + o_epk + i * 128);
-  });
-  // BN254 epoch keys: one subgroup check per DISTINCT key (honest batches carry one)
-  size_t U = 0;
-  int32_t* eidx = reinterpret_cast<int32_t*>(h + o_eidx);
-  if (bn) {
-    const uint8_t* E = h + o_epk;
-    uint8_t* UK = h + o_uk;
-    std::atomic<bool> same{true};
-    host_parallel_for(nch, [&](size_t c) {
-      for (size_t i = c * CH; i < std::min(n, (c + 1) * CH) && same.load(std::memory_order_relaxed); i++)
-        if (memcmp(E + i * 128, E, 128) != 0) same = false;
-    });
-    if (same) {
-      memcpy(UK, E, 128);
-      std::fill(eidx, eidx + n, 0);
-      U = 1;
-    } else {  // sort by (hash, bytes), then one entry per run of equal keys
-      std::vector<std::pair<uint64_t, uint32_t>> hk(n);
-      for (size_t i = 0; i < n; i++) {
-        uint64_t x = 0x9e3779b97f4a7c15ull;
-        for (int q = 0; q < 16; q++) {
-          uint64_t w;
-          memcpy(&w, E + i * 128 + 8 * q, 8);
-          x = (x ^ w) * 0xff51afd7ed558ccdull;
-          x ^= x >> 29;
-        }
-        hk[i] = {x, (uint32_t)i};
-      }
-      std::sort(hk.begin(), hk.end(), [&](const std::pair<uint64_t, uint32_t>& a, const std::pair<uint64_t, uint32_t>& b) {
-        if (a.first != b.first) return a.first < b.first;
-        return memcmp(E + (size_t)a.second * 128, E + (size_t)b.second * 128, 128) < 0;
-      });
-      for (size_t j = 0; j < n; j++) {
-        const uint32_t i = hk[j].second;
-        if (j == 0 || hk[j].first != hk[j - 1].first ||
-            memcmp(E + (size_t)i * 128, E + (size_t)hk[j - 1].second * 128, 128) != 0)
-          memcpy(UK + 128 * U++, E + (size_t)i * 128, 128);
-        eidx[i] = (int32_t)(U - 1);
-      }
-    }
-  }
-  // cached key verdicts; the misses are checked on the device and cached after the call
-  int32_t* gk = reinterpret_cast<int32_t*>(h + o_gk);
-  int32_t* miss = reinterpret_cast<int32_t*>(h + o_miss);
-  size_t M = 0;
-  if (bn) {
-    std::lock_guard<std::mutex> l(K->ring.mu);
-    for (size_t j = 0; j < U; j++) {
-      const auto it = K->g2_seen.find(std::string(reinterpret_cast<const char*>(h + o_uk + 128 * j), 128));
-      if (it != K->g2_seen.end()) {
-        gk[j] = it->second;
-      } else {
-        gk[j] = 0;
-        miss[M++] = (int32_t)j;
-      }
-    }
-  }
-  uint8_t* d = D.d_buf.as<uint8_t>();
-  ICHK(hipMemcpyAsync(d, h, o_uk + U * 128, hipMemcpyHostToDevice, D.stream));
-  ICHK(hipEventRecord(D.ev[0], D.stream));
-  // batch pairing check: group sums, one pairing product per group, the identities
-  // of failing groups listed for k_idv_pairing
-  uint32_t* scr = reinterpret_cast<uint32_t*>(d + o_scr);
-  const size_t ng = (n + BP_G - 1) / BP_G;
-  Chain c;
-  c.s = D.stream, c.n = (int)n, c.rec = reinterpret_cast<const uint32_t*>(d), c.pts = d + o_pts, c.epk = d + o_epk;
-  c.scr = scr, c.pin = reinterpret_cast<uint32_t*>(d + o_pin);
-  c.zk = reinterpret_cast<int32_t*>(d + o_zk), c.st = reinterpret_cast<int32_t*>(d + o_st);
-  int32_t* g2ok = reinterpret_cast<int32_t*>(d + o_g2ok);
-  c.eidx = bn ? reinterpret_cast<const int32_t*>(d + o_eidx) : nullptr, c.g2ok = bn ? g2ok : nullptr;
-  c.tables = K->d_tables.as<uint32_t>(), c.hash = K->d_hash.as<uint32_t>(), c.lines = K->d_lines.as<uint32_t>(), c.msg = d + o_msg;
-  c.gok = reinterpret_cast<int32_t*>(scr + bp_gok_off(n, ng));
-  c.cnt = reinterpret_cast<int32_t*>(scr + bp_cnt_off(n, ng));
-  c.list = reinterpret_cast<int32_t*>(scr + bp_list_off(n, ng));
-  if (K->batch && getrandom(c.key.k, sizeof c.key.k, 0) != (ssize_t)sizeof c.key.k) return FTS_API_EDEVICE;
-  if (bn) {
-    ICHK(hipMemcpyAsync(g2ok, gk, U * 4, hipMemcpyHostToDevice, D.stream));
-    if (M) {
-      ICHK(hipMemcpyAsync(g2ok + U, miss, M * 4, hipMemcpyHostToDevice, D.stream));
-      k_idv_g2_check<<<(unsigned)((M + 63) / 64), 64, 0, D.stream>>>((int)M, g2ok + U, d + o_uk, g2ok);
-    }
-  }
-  bn ? launch_tvals<BnCurve>(c) : launch_tvals<FbnCurve>(c);
-  ICHK(hipEventRecord(D.ev[1], D.stream));
-  unsigned nlist = 0;  // identities of failing groups (read back after k_idv_bp_sel)
-  if (K->batch) {
-    bn ? launch_batch<BnCurve>(c) : launch_batch<FbnCurve>(c);
-    ICHK(hipMemcpyAsync(h + o_cnt, c.cnt, 4, hipMemcpyDeviceToHost, D.stream));
-    ICHK(hipStreamSynchronize(D.stream));
-    nlist = *reinterpret_cast<const uint32_t*>(h + o_cnt);
-    // exact grid: idle pairing waves (256 VGPRs and scratch each) would still queue
-    // behind the other slots' kernels
-    if (nlist) bn ? launch_pairing<BnCurve>(c, nlist, true) : launch_pairing<FbnCurve>(c, nlist, true);
-  } else {
-    bn ? launch_pairing<BnCurve>(c, (unsigned)n, false) : launch_pairing<FbnCurve>(c, (unsigned)n, false);
-  }
-  ICHK(hipGetLastError());
-  ICHK(hipEventRecord(D.ev[2], D.stream));
-  ICHK(hipMemcpyAsync(h + o_st, d + o_st, st_b, hipMemcpyDeviceToHost, D.stream));
-  if (M) ICHK(hipMemcpyAsync(gk, g2ok, U * 4, hipMemcpyDeviceToHost, D.stream));
-  ICHK(hipStreamSynchronize(D.stream));
-  memcpy(status, h + o_st, st_b);
-  D.stats[0] = K->batch ? (uint32_t)ng : 0u;
-  D.stats[1] = K->batch ? nlist : (uint32_t)n;
-  if (M) {
-    std::lock_guard<std::mutex> l(K->ring.mu);
-    if (K->g2_seen.size() + M > 4096) K->g2_seen.clear();  // bounded: a new epoch's keys refill it
-    for (size_t q = 0; q < M; q++) {
-      const size_t j = (size_t)miss[q];
-      K->g2_seen.emplace(std::string(reinterpret_cast<const char*>(h + o_uk + 128 * j), 128), gk[j]);
-    }
-  }
-  ICHK(hipEventElapsedTime(&D.ms[0], D.ev[0], D.ev[1]));
-  ICHK(hipEventElapsedTime(&D.ms[1], D.ev[1], D.ev[2]));
-  return FTS_API_OK;
-}
-
-int fts_idemix_identity_last_timings(fts_idemix_idv* K, float* ms) {
-  if (!K || !ms) return FTS_API_EINVAL;
-  std::lock_guard<std::mutex> l(K->ring.mu);
-  ms[0] = K->last_ms[0], ms[1] = K->last_ms[1];
-  return FTS_API_OK;
-}
-
-int fts_idemix_identity_last_stats(fts_idemix_idv* K, uint32_t* out) {
-  if (!K || !out) return FTS_API_EINVAL;
-  std::lock_guard<std::mutex> l(K->ring.mu);
-  out[0] = K->last_stats[0], out[1] = K->last_stats[1];
-  return FTS_API_OK;
-}
-
-int fts_idemix_pairing_debug(fts_idemix_idv* K, int which, const uint8_t* p64, int final_exp, uint32_t* out192) {
-  using namespace idv;
-  if (!K || !p64 || !out192 || (which != 0 && which != 1)) return FTS_API_EINVAL;
-  const bool bn = K->curve == FTS_CURVE_BN254;
-  // P: 64 raw BE bytes -> affine Montgomery (host for BN254; device converts FP256BN)
-  uint32_t pm[16];
-  if (bn) {
-    host::G1A a;
-    if (!host::g1_from_bytes(p64, 64, a) || a.inf) return FTS_API_EINVAL;
-    memcpy(pm, a.x.v, 32);
-    memcpy(pm + 8, a.y.v, 32);
-  } else {
-    return FTS_API_EINVAL;  // FP256BN points go through fts_idemix_pairing_debug_mont
-  }
-  std::lock_guard<std::mutex> l(K->ring.mu);
-  ICHK(hipSetDevice(K->device));
-  // private stream and buffers, released on every exit path
-  struct Res {
-    Stream s;
-    DevBuf p, o;
-    ~Res() {
-      if (s) (void)hipStreamSynchronize(s);
-    }
-  } r;
-  ICHK(r.s.create());
-  if (!r.p.reserve(64) || !r.o.reserve(192 * 4)) return FTS_API_EDEVICE;
-  ICHK(hipMemcpyAsync(r.p.p, pm, 64, hipMemcpyHostToDevice, r.s));
-  k_idv_pairing_debug<BnCurve><<<1, 64, 0, r.s>>>(K->d_lines.as<uint32_t>(), which, r.p.as<uint32_t>(),
-                                                  r.o.as<uint32_t>(), final_exp);
-  ICHK(hipGetLastError());
-  ICHK(hipMemcpyAsync(out192, r.o.p, 192 * 4, hipMemcpyDeviceToHost, r.s));
-  ICHK(hipStreamSynchronize(r.s));
-  return FTS_API_OK;
-}
-
-}  // extern "C"
-#endif  // IDV_FBN_TU

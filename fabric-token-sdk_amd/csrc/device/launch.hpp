@@ -2,8 +2,8 @@
 // launchers, their size functions and the process-wide launch knobs.  Included
 // by the unit that defines a name and by every unit that uses it, so a changed
 // parameter, default argument or variable type fails to compile instead of
-// surfacing at link time (or never).  The structures are only named here; a
-// unit includes the header that defines the ones it touches.
+// surfacing at link time (or never).  The structures are only named here (but
+// idv::Chain, at the end); a unit includes the header that defines the ones it touches.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -90,8 +90,58 @@ void launch_sigma_prove(const SpDev& d, hipStream_t s);
 void launch_open_check(int n, const uint8_t* raw, const uint32_t* sc, const uint32_t* tables, int nb,
                        int32_t* status, hipStream_t s);
 
-// ---- idemix_kernels.hip (FP256BN fixed-base tables, shared with idemix_identity.hip)
+// ---- idemix_kernels.hip (nym signatures; the FP256BN fixed-base tables also serve the identity proofs)
 void fbn_build_tables(const uint32_t* plain, int nb, uint32_t* mont, int32_t* ok, uint32_t* tables, hipStream_t s);
 size_t fbn_words_per_base();
+// one tile of k_nym_verify (bn; msgw = the messages) or k_nym_verify_fbn (msgw = the hashed streams, ipk_hash unused)
+void launch_nym_verify(bool bn, int n, const uint32_t* rec, const uint8_t* nym, const uint32_t* msgw,
+                       const uint64_t* moff, const uint32_t* mlen, const uint32_t* tables, const uint32_t* ipk_hash,
+                       uint32_t* vtab, int32_t* status, int base, int tile, hipStream_t s);
 
 }  // namespace fts
+
+// ---- idemix_identity_bn.hip, idemix_identity_fbn.hip (device/idv_kernels.hpp)
+namespace idv {
+struct BnCurve;
+struct FbnCurve;
+constexpr int MSG_MAX = 832;  // transcript bytes per identity: 13 SHA-256 blocks (FP256BN: 19 + 11 * 65 + 36 = 770)
+constexpr int BP_G = 256;     // identities per group of the batch pairing check
+struct Key8 {
+  uint32_t k[8];
+};
+// one call's buffers (the only structure defined here: the host fills it and must not see the kernels)
+struct Chain {
+  hipStream_t s;
+  int n;
+  const uint32_t* rec;
+  const uint8_t *pts, *epk;
+  uint32_t *scr, *pin;
+  int32_t *zk, *st;
+  const int32_t *eidx, *g2ok;  // BN254 epoch keys (FP256BN: null)
+  const uint32_t *tables, *hash, *lines;
+  uint8_t* msg;
+  int32_t *gok, *cnt, *list;
+  Key8 key;
+};
+// per curve, instantiated in that curve's unit
+template <class CV>
+void launch_tvals(const Chain& c);
+template <class CV>
+void launch_batch(const Chain& c);
+template <class CV>
+void launch_pairing(const Chain& c, unsigned lanes, bool list);
+template <class CV>
+void launch_lines(const uint8_t* w, uint32_t* lines, int32_t* ok, hipStream_t s);
+// BN254 only
+void launch_g2_check(int M, const int32_t* idx, const uint8_t* keys, int32_t* ok, hipStream_t s);
+void launch_pairing_debug(const uint32_t* lines, int which, const uint32_t* p16, uint32_t* out, int final_exp,
+                          hipStream_t s);
+// sizes (words): pairing lines per G2 point, the t-value kernels' scratch, the batch check's layout in it
+size_t line_words(bool bn);
+size_t idv_scratch_words(size_t n);
+size_t bp_part_off(size_t n);
+size_t bp_gok_off(size_t n, size_t ng);
+size_t bp_cnt_off(size_t n, size_t ng);
+size_t bp_list_off(size_t n, size_t ng);
+size_t bp_scratch_words(size_t n);
+}  // namespace idv

@@ -112,7 +112,7 @@ void parallel_for(size_t n, size_t min_parallel, F&& f) {
   HostPool::get().run(n, fn);
 }
 // the same pool for the signature batches' packing loops (ecdsa_kernels.hip,
-// idemix_kernels.hip, idemix_identity.hip)
+// api_idemix.cpp)
 void host_parallel_for(size_t n, const std::function<void(size_t)>& f);
 
 inline double now_ms() {

@@ -1,0 +1,226 @@
+// Stand-alone check of host/idemix_parse.hpp (over host/pb.hpp and host/u256.hpp),
+// the idemix verifiers' parsers of untrusted bytes, built with the host address and
+// undefined-behaviour sanitizers (any report is fatal).  No device, no library.
+// Every input lives in a heap block of exactly its length and every output (record,
+// points, epoch key) in a block of exactly its size, so a read or write past either
+// is a report.  Each input is parsed as it is, as every strict prefix, with every
+// byte flipped two ways (^0x01, ^0x80; every 16th byte for the `tile` identities)
+// and in the null / zero-length forms.
+//   idemix_parse_check <file of lines: kind curve hex [honest|tile]>
+//     kind: id | nym | ipk; curve: bn254 | fp256bn; honest, tile: an honest golden case
+//   prints a SHA-256 over every output of the run; exit status 0 iff every check holds
+#include <atomic>
+#include <cstdio>
+#include <cstdlib>
+#include <fstream>
+#include <memory>
+#include <sstream>
+#include <string>
+#include <thread>
+#include <vector>
+
+#include "../common/sha256.hpp"
+#include "../host/idemix_parse.hpp"
+
+using namespace idv;
+using fts::Sha256;
+
+static std::atomic<int> g_failed{0};
+#define CHECK(x)                                                                                \
+  do {                                                                                          \
+    if (!(x)) {                                                                                 \
+      if (g_failed++ < 20) fprintf(stderr, "idemix_parse_check: %s (line %d)\n", #x, __LINE__); \
+    }                                                                                           \
+  } while (0)
+
+enum Kind { ID, NYM, IPK };
+struct Input {
+  Kind kind;
+  bool bn, honest, tile;
+  std::string bytes;
+};
+struct Result {
+  uint8_t digest[32];
+  size_t calls = 0;
+};
+
+static void put32(Sha256& h, uint32_t v) {
+  const uint8_t b[4] = {(uint8_t)v, (uint8_t)(v >> 8), (uint8_t)(v >> 16), (uint8_t)(v >> 24)};
+  h.update(b, 4);
+}
+
+// ---- one call of each parser over exactly-sized blocks, its outputs hashed
+// (p == nullptr: the null form)
+static std::unique_ptr<uint8_t[]> exact(const uint8_t* p, size_t len) {
+  std::unique_ptr<uint8_t[]> b(new uint8_t[len]);
+  if (len) memcpy(b.get(), p, len);
+  return b;
+}
+static int32_t run_id(const uint8_t* p, size_t len, bool null, bool bn, uint32_t& flags, Sha256& h) {
+  const auto in = exact(p, null ? 0 : len);
+  std::unique_ptr<uint32_t[]> rec(new uint32_t[REC_STRIDE]);
+  std::unique_ptr<uint8_t[]> pts(new uint8_t[NPT * 64]), epk(new uint8_t[128]);
+  const int32_t st = parse_identity(null ? nullptr : in.get(), len, bn, rec.get(), pts.get(), epk.get());
+  flags = rec[R_FLAGS];
+  put32(h, (uint32_t)st);
+  h.update(reinterpret_cast<const uint8_t*>(rec.get()), REC_STRIDE * 4);
+  h.update(pts.get(), NPT * 64);
+  h.update(epk.get(), 128);
+  CHECK(st == FTS_OK || st == FTS_E_ID_MALFORMED || st == FTS_E_ID_BADNYM);
+  return st;
+}
+static int32_t run_nym(const uint8_t* p, size_t len, bool null, bool bn, Sha256& h) {
+  const auto in = exact(p, null ? 0 : len);
+  std::unique_ptr<uint32_t[]> rec(new uint32_t[NREC]);
+  const int32_t st = parse_nym_sig(null ? nullptr : in.get(), len, bn, rec.get());
+  put32(h, (uint32_t)st);
+  h.update(reinterpret_cast<const uint8_t*>(rec.get()), NREC * 4);
+  CHECK(st == FTS_OK || st == FTS_E_NYM_MALFORMED || st == FTS_E_NYM_INVALID);
+  return st;
+}
+// the issuer key's walk and every blob either creator extracts (accept bit, then the bytes)
+static void run_ipk(const uint8_t* p, size_t len, Sha256& h) {
+  const auto in = exact(p, len);
+  IpkFields f;
+  const bool ok = parse_ipk(in.get(), len, f);
+  put32(h, ok ? (uint32_t)f.n_attrs + 1u : 0u);
+  if (!ok) return;
+  std::unique_ptr<uint8_t[]> out(new uint8_t[64]), out2(new uint8_t[128]), h32(new uint8_t[32]);
+  const Span* pt[6] = {&f.h_sk, &f.h_rand, &f.h_attrs[0], &f.h_attrs[1], &f.h_attrs[2], &f.h_attrs[3]};
+  for (int q = 0; q < 6; q++)
+    for (int strict = 0; strict < 2; strict++) {
+      memset(out.get(), 0, 64);
+      put32(h, fts::ecp_xy(*pt[q], out.get(), strict != 0) ? 1u : 0u);
+      h.update(out.get(), 64);
+    }
+  memset(out2.get(), 0, 128);
+  put32(h, fts::ecp2_raw(f.w, out2.get()) ? 1u : 0u);
+  h.update(out2.get(), 128);
+  ipk_hash32(f, h32.get());
+  h.update(h32.get(), 32);
+}
+
+// ---- which prefixes of an identity may parse: from its field list, the cut must fall
+// on a boundary of the outer message; `nym` / `proof`: fields 1 / 4 lie before the cut
+struct Cut {
+  bool boundary = false, nym = false, proof = false;
+};
+static std::vector<Cut> identity_cuts(const std::string& id) {
+  std::vector<Cut> cuts(id.size() + 1);
+  Pb pb{reinterpret_cast<const uint8_t*>(id.data()), id.size()};
+  Pb::Field d;
+  Cut c;
+  while (pb.o < pb.n && pb.next(d)) {
+    c.boundary = true;
+    c.nym = c.nym || d.f == 1;
+    c.proof = c.proof || d.f == 4;
+    cuts[pb.o] = c;
+  }
+  return cuts;
+}
+
+static Result run_input(const Input& in) {
+  Result r;
+  Sha256 h;
+  h.init();
+  const uint8_t* p = reinterpret_cast<const uint8_t*>(in.bytes.data());
+  const size_t len = in.bytes.size();
+  const uint32_t bad = F_EARLY_MALFORMED | F_LATE_MALFORMED | F_NO_EID | F_NO_RH;
+  const std::vector<Cut> cuts = in.kind == ID ? identity_cuts(in.bytes) : std::vector<Cut>();
+  // k: prefix k; -1: the input itself; -2: a corrupted copy or a null / zero-length form
+  auto one = [&](const uint8_t* q, size_t l, bool null, long k) {
+    r.calls++;
+    if (in.kind == ID) {
+      uint32_t flags = 0;
+      const int32_t st = run_id(q, l, null, in.bn, flags, h);
+      if (k >= 0) {  // a strict prefix: never a clean record unless the field list allows it
+        const Cut& c = cuts[(size_t)k];
+        if (st == FTS_OK && !(flags & bad)) CHECK(c.boundary && c.nym && c.proof);
+        if (st == FTS_E_ID_BADNYM) CHECK(c.boundary && c.nym);
+      } else if (k == -1 && in.honest) {
+        CHECK(st == FTS_OK && flags == 0);
+      } else if (null || l == 0) {
+        CHECK(st == FTS_E_ID_MALFORMED);
+      }
+    } else if (in.kind == NYM) {
+      const int32_t st = run_nym(q, l, null, in.bn, h);
+      if (k == -1 && in.honest) CHECK(st == FTS_OK);
+      if (null || l == 0) CHECK(st == FTS_E_NYM_MALFORMED);
+    } else if (!null) {  // the creators reject a null key before parsing
+      run_ipk(q, l, h);
+    }
+  };
+  one(p, len, false, -1);
+  one(p, 0, false, -2);
+  one(nullptr, 0, true, -2);
+  one(nullptr, len, true, -2);
+  for (size_t k = 0; k < len; k++) one(p, k, false, (long)k);
+  std::string m = in.bytes;
+  for (size_t k = 0; k < len; k += in.tile ? 16 : 1)
+    for (uint8_t x : {(uint8_t)0x01, (uint8_t)0x80}) {
+      m[k] = (char)(in.bytes[k] ^ x);
+      one(reinterpret_cast<const uint8_t*>(m.data()), len, false, -2);
+      m[k] = in.bytes[k];
+    }
+  h.final(r.digest);
+  return r;
+}
+
+// the inputs' digests in input order -> the run's digest
+static std::string run_all(const std::vector<Input>& in, size_t threads, size_t& calls) {
+  std::vector<Result> res(in.size());
+  std::vector<std::thread> th;
+  for (size_t t = 0; t < threads; t++)
+    th.emplace_back([&, t] {
+      for (size_t i = t; i < in.size(); i += threads) res[i] = run_input(in[i]);
+    });
+  for (auto& x : th) x.join();
+  Sha256 h;
+  h.init();
+  calls = 0;
+  for (const Result& r : res) h.update(r.digest, 32), calls += r.calls;
+  uint8_t d[32];
+  h.final(d);
+  char hex[65];
+  for (int i = 0; i < 32; i++) snprintf(hex + 2 * i, 3, "%02x", d[i]);
+  return hex;
+}
+
+int main(int argc, char** argv) {
+  if (argc != 2) {
+    fprintf(stderr, "usage: idemix_parse_check <inputs>\n");
+    return 2;
+  }
+  std::ifstream f(argv[1]);
+  std::vector<Input> in;
+  std::string line;
+  while (std::getline(f, line)) {
+    std::istringstream ss(line);
+    std::string kind, curve, hex, mark;
+    if (!(ss >> kind >> curve)) continue;
+    ss >> hex >> mark;
+    if (hex == "-") hex.clear();
+    Input x;
+    x.kind = kind == "id" ? ID : kind == "nym" ? NYM : IPK;
+    x.bn = curve == "bn254";
+    x.tile = mark == "tile";
+    x.honest = x.tile || mark == "honest";
+    const bool known = (kind == "id" || kind == "nym" || kind == "ipk") && (x.bn || curve == "fp256bn") &&
+                       hex.size() % 2 == 0 && (mark.empty() || x.honest);
+    CHECK(known);
+    if (!known) continue;
+    for (size_t k = 0; k < hex.size(); k += 2) x.bytes.push_back((char)strtoul(hex.substr(k, 2).c_str(), nullptr, 16));
+    in.push_back(x);
+  }
+  CHECK(!in.empty());
+  size_t calls = 0, calls4 = 0;
+  const std::string serial = run_all(in, 1, calls), threaded = run_all(in, 4, calls4);
+  CHECK(serial == threaded && calls == calls4);
+  printf("idemix_parse_check: %zu inputs, %zu parser calls, sha256 %s\n", in.size(), calls, serial.c_str());
+  if (g_failed) {
+    fprintf(stderr, "idemix_parse_check: %d checks failed\n", g_failed.load());
+    return 1;
+  }
+  printf("idemix_parse_check: ok\n");
+  return 0;
+}

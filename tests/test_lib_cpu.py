@@ -49,6 +49,41 @@ def test_action_stage_check():
     assert "stage_check: ok" in out.stdout
 
 
+def test_idemix_parse_check(tmp_path):
+    """lib/idemix_parse_check (csrc/tools/idemix_parse_check.cpp): the idemix
+    parsers (host/idemix_parse.hpp) on the golden identities, nym signatures and
+    issuer keys, the wire edge cases, every strict prefix and single-byte
+    corruptions, as a plain program built with the host address / undefined-
+    behaviour sanitizers (a report aborts it)"""
+    import json
+    from idemix_wire_cases import wire_edge_cases
+    gold = os.path.join(ROOT, "tests", "golden")
+    lines = []
+    with open(os.path.join(gold, "idemix_identity_golden.json")) as f:
+        doc = json.load(f)
+    for tag in ("bn254", "fp256bn"):
+        for c in doc[tag]["cases"]:
+            lines.append(("id", tag, c["identity"], "honest" if c["name"].startswith("honest_") else ""))
+        lines += [("id", tag, c["identity"], "tile") for c in doc[tag]["tile"]]
+        honest = bytes.fromhex({c["name"]: c for c in doc[tag]["cases"]}["honest_1"]["identity"])
+        lines += [("id", tag, raw.hex(), "") for raw, _ in wire_edge_cases(honest, 19)]
+    with open(os.path.join(gold, "idemix_golden.json")) as f:
+        doc = json.load(f)
+    for tag in ("bn254", "fp256bn"):
+        for c in doc[tag]["cases"]:
+            lines.append(("nym", tag, c["sig"], "honest" if c["name"].startswith("honest_") else ""))
+    for d in sorted(os.listdir(os.path.join(gold, "idemix"))):
+        with open(os.path.join(gold, "idemix", d, "IssuerPublicKey"), "rb") as f:
+            lines.append(("ipk", d.split("_")[0], f.read().hex(), ""))
+    assert len([l for l in lines if l[0] == "ipk"]) == 4
+    inp = tmp_path / "inputs.txt"
+    inp.write_text("".join("%s %s %s %s\n" % (k, t, h or "-", m) for k, t, h, m in lines))
+    exe = os.path.join(ROOT, "fabric-token-sdk_amd", "lib", "idemix_parse_check")
+    out = subprocess.run([exe, str(inp)], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0, out.stdout + out.stderr
+    assert "idemix_parse_check: ok" in out.stdout
+
+
 def test_status_strings():
     from fts_gpu import _lib as L
     assert L.status_str(L.FTS_E_RP_INVALID) == "invalid range proof"
