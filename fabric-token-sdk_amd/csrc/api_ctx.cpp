@@ -391,6 +391,13 @@ const char* fts_status_str(int32_t s) {
     case FTS_E_ID_APRIME: return "signature invalid: APrime = 1";
     case FTS_E_ID_PAIRING: return "signature invalid: APrime and ABar don't have the expected structure";
     case FTS_E_ID_ZK: return "signature invalid: zero-knowledge proof is invalid";
+    case FTS_E_AUDIT_MALFORMED: return "could not deserialize the identity, its proof or the audit data";
+    case FTS_E_AUDIT_NO_EIDNYM: return "error while verifying the nym eid: no EidNym provided";
+    case FTS_E_AUDIT_EID_POINT: return "error while verifying the nym eid: invalid EidNym point";
+    case FTS_E_AUDIT_EID_MISMATCH: return "error while verifying the nym eid: eid nym does not match";
+    case FTS_E_AUDIT_NO_RHNYM: return "error while verifying the nym rh: no RhNym provided";
+    case FTS_E_AUDIT_RH_POINT: return "error while verifying the nym rh: invalid RhNym point";
+    case FTS_E_AUDIT_RH_MISMATCH: return "error while verifying the nym rh: rh nym does not match";
     default: return "unknown status";
   }
 }

@@ -57,6 +57,15 @@ struct IdvSlot {
   uint32_t stats[2] = {0u, 0u};
 };
 
+constexpr int AUD_NSLOT = 3;  // audit-match calls in flight per handle, beside the identity slots
+struct AuditSlot {
+  Stream stream;
+  DevBuf d_buf;  // pts | rnd | aoff | alen | pre | rh_pre | strings | half_st
+  PinBuf h_buf;  // pinned staging of the same layout
+  Event ev[2];
+  float ms = 0.f;
+};
+
 // 32 bytes -> 8 big-endian words
 void be_words(const uint8_t h[32], uint32_t hw[8]) {
   for (int q = 0; q < 8; q++)
@@ -113,6 +122,10 @@ struct fts_idemix_idv {
   // verdict): an honest stream carries one key per epoch, and k_idv_g2_check is
   // one 254-step G2 chain on one lane (7.7 ms, on the call's critical path)
   std::unordered_map<std::string, int32_t> g2_seen;
+  // audit info matching (fts_idemix_audit_match_batch): slots of its own, so a match
+  // never waits for (or holds) an identity-verification slot
+  SlotRing<AuditSlot, AUD_NSLOT> aud;
+  float aud_ms = 0.f;  // under aud.mu
   ~fts_idemix_idv() {
     if (device >= 0) (void)hipSetDevice(device);
   }
@@ -354,6 +367,10 @@ int fts_idemix_idv_create(int device, const uint8_t* ipk, size_t ipk_len, int cu
     ok = ok && S.stream.create() == hipSuccess;
     for (auto& e : S.ev) ok = ok && e.create() == hipSuccess;
   }
+  for (auto& S : k->aud.slot) {
+    ok = ok && S.stream.create() == hipSuccess;
+    for (auto& e : S.ev) ok = ok && e.create() == hipSuccess;
+  }
   if (!ok) return FTS_API_EDEVICE;
   *out = k.release();
   return FTS_API_OK;
@@ -523,6 +540,91 @@ int fts_idemix_identity_last_stats(fts_idemix_idv* K, uint32_t* out) {
   if (!K || !out) return FTS_API_EINVAL;
   std::lock_guard<std::mutex> l(K->ring.mu);
   out[0] = K->last_stats[0], out[1] = K->last_stats[1];
+  return FTS_API_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Audit info against owner identities (AuditInfo.Match)
+// ---------------------------------------------------------------------------
+int fts_idemix_audit_match_batch(fts_idemix_idv* K, size_t n, const fts_idemix_audit_item* items, int32_t* status) {
+  if (!K || n > (size_t)(1u << 22) || (n && (!items || !status))) return FTS_API_EINVAL;
+  if (n == 0) return FTS_API_OK;
+  const bool bn = K->curve == FTS_CURVE_BN254;
+  // a lane's string: its bytes padded to whole words + 1 (as the nym messages)
+  auto words = [](size_t len) { return (len + 3) / 4 + 1; };
+  size_t atot_w = 0;
+  for (size_t i = 0; i < n; i++) {
+    const fts_idemix_audit_item& it = items[i];
+    if (it.eid_len > 0xffffff00u || it.rh_len > 0xffffff00u || (it.eid_len && !it.eid) || (it.rh_len && !it.rh))
+      return FTS_API_EINVAL;
+    atot_w += words(it.eid_len) + words(it.rh_len);
+  }
+  auto guard = K->aud.acquire([K](AuditSlot& S) { K->aud_ms = S.ms; });
+  AuditSlot& D = guard.slot();
+  ICHK(hipSetDevice(K->device));
+  // half-major lanes g = half * n + i: pts | rnd | aoff | alen (2n each) | pre | rh_pre (n each) |
+  // strings (the EID strings, then the RH strings) | half_st (2n, written by the device)
+  const size_t o_rnd = 2 * n * 64, o_off = o_rnd + 2 * n * 32, o_len = o_off + 2 * n * 8, o_pre = o_len + 2 * n * 4,
+               o_rhp = o_pre + n * 4, o_str = (o_rhp + n * 4 + 255) & ~size_t(255),
+               o_hst = (o_str + atot_w * 4 + 255) & ~size_t(255), need = o_hst + 2 * n * 4;
+  if (D.h_buf.cap < need && !D.h_buf.reserve(need + need / 2)) return FTS_API_ENOMEM;
+  if (D.d_buf.cap < need && !D.d_buf.reserve(need + need / 2)) return FTS_API_ENOMEM;
+  uint8_t* h = D.h_buf.as<uint8_t>();
+  uint64_t* hoff = reinterpret_cast<uint64_t*>(h + o_off);
+  {
+    uint64_t o = 0;
+    for (size_t i = 0; i < n; i++) hoff[i] = o, o += words(items[i].eid_len);
+    for (size_t i = 0; i < n; i++) hoff[n + i] = o, o += words(items[i].rh_len);
+  }
+  auto pack = [&](size_t lo, size_t hi) {
+    for (size_t i = lo; i < hi; i++) {
+      const fts_idemix_audit_item& it = items[i];
+      int32_t rh_pre = FTS_OK;
+      int32_t pre = parse_audit_identity(it.id, it.id_len, bn, h + i * 64, h + (n + i) * 64, rh_pre);
+      if (!it.r_eid32 || !it.r_rh32) pre = FTS_E_AUDIT_MALFORMED;  // the reference dereferences a nil Rand
+      reinterpret_cast<int32_t*>(h + o_pre)[i] = pre;
+      reinterpret_cast<int32_t*>(h + o_rhp)[i] = rh_pre;
+      const uint8_t* const rnd[2] = {it.r_eid32, it.r_rh32};
+      const uint8_t* const str[2] = {it.eid, it.rh};
+      const size_t slen[2] = {it.eid_len, it.rh_len};
+      for (int half = 0; half < 2; half++) {
+        const size_t g = (size_t)half * n + i;
+        uint8_t* r = h + o_rnd + g * 32;
+        if (rnd[half]) memcpy(r, rnd[half], 32);
+        else memset(r, 0, 32);
+        reinterpret_cast<uint32_t*>(h + o_len)[g] = (uint32_t)slen[half];
+        uint8_t* sw = h + o_str + hoff[g] * 4;
+        if (slen[half]) memcpy(sw, str[half], slen[half]);
+        memset(sw + slen[half], 0, words(slen[half]) * 4 - slen[half]);
+      }
+    }
+  };
+  const size_t CH = 2048, nch = (n + CH - 1) / CH;
+  host_parallel_for(nch, [&](size_t c) { pack(c * CH, std::min(n, (c + 1) * CH)); });
+  uint8_t* d = D.d_buf.as<uint8_t>();
+  ICHK(hipMemcpyAsync(d, h, o_hst, hipMemcpyHostToDevice, D.stream));
+  ICHK(hipEventRecord(D.ev[0], D.stream));
+  launch_idv_audit(bn, (int)n, d, reinterpret_cast<const uint32_t*>(d + o_rnd),
+                   reinterpret_cast<const uint32_t*>(d + o_str), reinterpret_cast<const uint64_t*>(d + o_off),
+                   reinterpret_cast<const uint32_t*>(d + o_len), reinterpret_cast<const int32_t*>(d + o_pre),
+                   reinterpret_cast<const int32_t*>(d + o_rhp), K->d_tables.as<uint32_t>(),
+                   reinterpret_cast<int32_t*>(d + o_hst), D.stream);
+  ICHK(hipGetLastError());
+  ICHK(hipEventRecord(D.ev[1], D.stream));
+  ICHK(hipMemcpyAsync(h + o_hst, d + o_hst, 2 * n * 4, hipMemcpyDeviceToHost, D.stream));
+  ICHK(hipStreamSynchronize(D.stream));
+  // the reference's order: what ends the match on the host, every EID check, every RH check
+  const int32_t* pre = reinterpret_cast<const int32_t*>(h + o_pre);
+  const int32_t* hst = reinterpret_cast<const int32_t*>(h + o_hst);
+  for (size_t i = 0; i < n; i++) status[i] = pre[i] ? pre[i] : hst[i] ? hst[i] : hst[n + i];
+  ICHK(hipEventElapsedTime(&D.ms, D.ev[0], D.ev[1]));
+  return FTS_API_OK;
+}
+
+int fts_idemix_audit_last_timings(fts_idemix_idv* K, float* ms) {
+  if (!K || !ms) return FTS_API_EINVAL;
+  std::lock_guard<std::mutex> l(K->aud.mu);
+  *ms = K->aud_ms;
   return FTS_API_OK;
 }
 

@@ -144,4 +144,10 @@ size_t bp_gok_off(size_t n, size_t ng);
 size_t bp_cnt_off(size_t n, size_t ng);
 size_t bp_list_off(size_t n, size_t ng);
 size_t bp_scratch_words(size_t n);
+
+// ---- idemix_audit.hip (device/idv_audit.hpp): k_idv_audit of either curve, 2n lanes
+// (pts, rnd, aoff, alen and half_st are [2][n], half-major; pre and rh_pre [n])
+void launch_idv_audit(bool bn, int n, const uint8_t* pts, const uint32_t* rnd, const uint32_t* attrw,
+                      const uint64_t* aoff, const uint32_t* alen, const int32_t* pre, const int32_t* rh_pre,
+                      const uint32_t* tables, int32_t* half_st, hipStream_t s);
 }  // namespace idv

@@ -224,6 +224,116 @@ inline int32_t parse_identity(const uint8_t* id, size_t len, bool bn, uint32_t* 
   return FTS_OK;
 }
 
+// ------------------------------------------------------- audit info matching
+// AuditInfo.Match (idemix/crypto/audit.go:40-84) reads an identity far more loosely
+// than Signature.Ver: proto.Unmarshal of SerializedIdemixIdentity and of its whole
+// Signature (embedded messages included), then only EidNym.Nym and RhNym.Nym.  No
+// scalar is parsed, no other point decoded, the nym public key never read -- so none
+// of parse_identity's scalar or point rules apply here.
+namespace audit_wire {
+// every field of an embedded message on the wire, the known ones with their wire type:
+// `bytes_lo..bytes_hi` length-delimited, `varint_f` (0: none) a varint
+inline bool msg_ok(const Span& s, uint32_t bytes_lo, uint32_t bytes_hi, uint32_t varint_f) {
+  Pb pb{s.p, s.n};
+  Pb::Field d;
+  while (pb.o < pb.n) {
+    if (!pb.next(d)) return false;
+    if (d.f >= bytes_lo && d.f <= bytes_hi && d.wt != 2) return false;
+    if (varint_f && d.f == varint_f && d.wt != 0) return false;
+  }
+  return true;
+}
+// a merged ECP{1 x, 2 y}: proto3 merges the occurrences of an embedded message, the
+// last x and the last y win
+struct Ecp {
+  Span x, y;
+  bool set = false;  // the message field was seen (a non-nil *ECP)
+  bool merge(const Span& s) {
+    set = true;
+    Pb pb{s.p, s.n};
+    Pb::Field d;
+    while (pb.o < pb.n) {
+      if (!pb.next(d)) return false;
+      if ((d.f == 1 || d.f == 2) && d.wt != 2) return false;
+      if (d.f == 1) x = Span{d.v, d.vl, true};
+      if (d.f == 2) y = Span{d.v, d.vl, true};
+    }
+    return true;
+  }
+  // G1FromProto's length rule (its canonical / on-curve rules run on the device)
+  bool raw(uint8_t out[64]) const {
+    if (x.n != 32 || y.n != 32) return false;
+    memcpy(out, x.p, 32);
+    memcpy(out + 32, y.p, 32);
+    return true;
+  }
+};
+// EidNym / RhNym {1 nym (ECP), 2 proof_s}: one occurrence merged into `nym`
+inline bool nym_merge(const Span& s, Ecp& nym) {
+  Pb pb{s.p, s.n};
+  Pb::Field d;
+  while (pb.o < pb.n) {
+    if (!pb.next(d)) return false;
+    if ((d.f == 1 || d.f == 2) && d.wt != 2) return false;
+    if (d.f == 1 && !nym.merge(Span{d.v, d.vl, true})) return false;
+  }
+  return true;
+}
+}  // namespace audit_wire
+
+// SerializedIdemixIdentity -> the status known before the device and the raw EidNym /
+// RhNym points (64 bytes each, zeroed unless the call returns FTS_OK and, for rh_pt,
+// rh_pre is FTS_OK too).  Returns FTS_OK, FTS_E_AUDIT_MALFORMED, FTS_E_AUDIT_NO_EIDNYM
+// or FTS_E_AUDIT_EID_POINT (a coordinate that is not 32 bytes); these end the match.
+// rh_pre <- FTS_OK, FTS_E_AUDIT_NO_RHNYM or FTS_E_AUDIT_RH_POINT: the RH half's verdict
+// as far as the host knows it, which counts only after the EID half has passed on the
+// device (all EID checks precede all RH checks).  No allocation.
+inline int32_t parse_audit_identity(const uint8_t* id, size_t len, bool bn, uint8_t eid_pt[64], uint8_t rh_pt[64],
+                                    int32_t& rh_pre) {
+  using namespace audit_wire;
+  (void)bn;  // the wire rules are the same on both curves; the point rules differ on the device
+  memset(eid_pt, 0, 64);
+  memset(rh_pt, 0, 64);
+  rh_pre = FTS_OK;
+  if (!id) return FTS_E_AUDIT_MALFORMED;
+  Pb::Field d;
+  Span proof;
+  {
+    Pb pb{id, len};
+    while (pb.o < pb.n) {
+      if (!pb.next(d)) return FTS_E_AUDIT_MALFORMED;
+      if (d.f >= 1 && d.f <= 4 && d.wt != 2) return FTS_E_AUDIT_MALFORMED;
+      if (d.f == 4) proof = Span{d.v, d.vl, true};
+    }
+  }
+  if (proof.n == 0) return FTS_E_AUDIT_MALFORMED;  // "invalid signature, it must not be empty"
+  // Signature (field numbers as in parse_identity): 1 2 3 12 ECP, 14 ECP2 {1..4},
+  // 17 NonRevocationProof {1 revocation_alg (varint), 2 non_revocation_proof}, 18 19 the
+  // nyms, 16 epoch (varint), every other field up to 19 bytes
+  Ecp eid, rh;
+  Pb pb{proof.p, proof.n};
+  while (pb.o < pb.n) {
+    if (!pb.next(d) || (d.f >= 1 && d.f <= 19 && d.f != 16 && d.wt != 2) || (d.f == 16 && d.wt != 0))
+      return FTS_E_AUDIT_MALFORMED;
+    const Span s{d.v, d.vl, true};
+    bool ok = true;
+    switch (d.f) {
+      case 1: case 2: case 3: case 12: ok = msg_ok(s, 1, 2, 0); break;
+      case 14: ok = msg_ok(s, 1, 4, 0); break;
+      case 17: ok = msg_ok(s, 2, 2, 1); break;
+      case 18: ok = nym_merge(s, eid); break;
+      case 19: ok = nym_merge(s, rh); break;
+      default: break;
+    }
+    if (!ok) return FTS_E_AUDIT_MALFORMED;
+  }
+  if (!eid.set) return FTS_E_AUDIT_NO_EIDNYM;  // sig.EidNym == nil || sig.EidNym.Nym == nil
+  if (!eid.raw(eid_pt)) return FTS_E_AUDIT_EID_POINT;
+  if (!rh.set) rh_pre = FTS_E_AUDIT_NO_RHNYM;
+  else if (!rh.raw(rh_pt)) rh_pre = FTS_E_AUDIT_RH_POINT;
+  return FTS_OK;
+}
+
 // IssuerPublicKey: 2 h_sk, 3 h_rand, 4 h_attrs (repeated ECP), 5 w (ECP2), 10 hash;
 // a field with another wire type is ignored.  false: proto.Unmarshal fails.  Each
 // creator applies its own acceptance rule to the spans.

@@ -7,8 +7,10 @@
 // byte flipped two ways (^0x01, ^0x80; every 16th byte for the `tile` identities)
 // and in the null / zero-length forms.
 //   idemix_parse_check <file of lines: kind curve hex [honest|tile]>
-//     kind: id | nym | ipk; curve: bn254 | fp256bn; honest, tile: an honest golden case
-//   prints a SHA-256 over every output of the run; exit status 0 iff every check holds
+//     kind: id | nym | ipk | audit; curve: bn254 | fp256bn; honest, tile: an honest golden case
+//     (audit: an identity read by parse_audit_identity, the audit-info matcher's parser)
+//   prints "audit <input index> <pre> <rh_pre>" for every audit input as given, then a
+//   SHA-256 over every output of the run; exit status 0 iff every check holds
 #include <atomic>
 #include <cstdio>
 #include <cstdlib>
@@ -33,7 +35,7 @@ static std::atomic<int> g_failed{0};
     }                                                                                           \
   } while (0)
 
-enum Kind { ID, NYM, IPK };
+enum Kind { ID, NYM, IPK, AUDIT };
 struct Input {
   Kind kind;
   bool bn, honest, tile;
@@ -42,6 +44,7 @@ struct Input {
 struct Result {
   uint8_t digest[32];
   size_t calls = 0;
+  int32_t pre = 0, rh_pre = 0;  // audit: the statuses of the input as given
 };
 
 static void put32(Sha256& h, uint32_t v) {
@@ -76,6 +79,22 @@ static int32_t run_nym(const uint8_t* p, size_t len, bool null, bool bn, Sha256&
   put32(h, (uint32_t)st);
   h.update(reinterpret_cast<const uint8_t*>(rec.get()), NREC * 4);
   CHECK(st == FTS_OK || st == FTS_E_NYM_MALFORMED || st == FTS_E_NYM_INVALID);
+  return st;
+}
+static int32_t run_audit(const uint8_t* p, size_t len, bool null, bool bn, int32_t& rh_pre, Sha256& h) {
+  const auto in = exact(p, null ? 0 : len);
+  std::unique_ptr<uint8_t[]> eid(new uint8_t[64]), rh(new uint8_t[64]);
+  const int32_t st = parse_audit_identity(null ? nullptr : in.get(), len, bn, eid.get(), rh.get(), rh_pre);
+  put32(h, (uint32_t)st);
+  put32(h, (uint32_t)rh_pre);
+  h.update(eid.get(), 64);
+  h.update(rh.get(), 64);
+  CHECK(st == FTS_OK || st == FTS_E_AUDIT_MALFORMED || st == FTS_E_AUDIT_NO_EIDNYM || st == FTS_E_AUDIT_EID_POINT);
+  CHECK(rh_pre == FTS_OK || (st == FTS_OK && (rh_pre == FTS_E_AUDIT_NO_RHNYM || rh_pre == FTS_E_AUDIT_RH_POINT)));
+  // a point is handed over only with a clean status for its half
+  const uint8_t zero[64] = {0};
+  if (st != FTS_OK) CHECK(memcmp(eid.get(), zero, 64) == 0);
+  if (st != FTS_OK || rh_pre != FTS_OK) CHECK(memcmp(rh.get(), zero, 64) == 0);
   return st;
 }
 // the issuer key's walk and every blob either creator extracts (accept bit, then the bytes)
@@ -126,7 +145,7 @@ static Result run_input(const Input& in) {
   const uint8_t* p = reinterpret_cast<const uint8_t*>(in.bytes.data());
   const size_t len = in.bytes.size();
   const uint32_t bad = F_EARLY_MALFORMED | F_LATE_MALFORMED | F_NO_EID | F_NO_RH;
-  const std::vector<Cut> cuts = in.kind == ID ? identity_cuts(in.bytes) : std::vector<Cut>();
+  const std::vector<Cut> cuts = in.kind == ID || in.kind == AUDIT ? identity_cuts(in.bytes) : std::vector<Cut>();
   // k: prefix k; -1: the input itself; -2: a corrupted copy or a null / zero-length form
   auto one = [&](const uint8_t* q, size_t l, bool null, long k) {
     r.calls++;
@@ -141,6 +160,17 @@ static Result run_input(const Input& in) {
         CHECK(st == FTS_OK && flags == 0);
       } else if (null || l == 0) {
         CHECK(st == FTS_E_ID_MALFORMED);
+      }
+    } else if (in.kind == AUDIT) {
+      int32_t rh_pre = 0;
+      const int32_t st = run_audit(q, l, null, in.bn, rh_pre, h);
+      if (k >= 0) {  // a strict prefix parses only at a field boundary past the proof (the nym key is not read)
+        if (st != FTS_E_AUDIT_MALFORMED) CHECK(cuts[(size_t)k].boundary && cuts[(size_t)k].proof);
+      } else if (k == -1) {
+        r.pre = st, r.rh_pre = rh_pre;
+        if (in.honest) CHECK(st == FTS_OK && rh_pre == FTS_OK);
+      } else if (null || l == 0) {
+        CHECK(st == FTS_E_AUDIT_MALFORMED);
       }
     } else if (in.kind == NYM) {
       const int32_t st = run_nym(q, l, null, in.bn, h);
@@ -167,8 +197,8 @@ static Result run_input(const Input& in) {
 }
 
 // the inputs' digests in input order -> the run's digest
-static std::string run_all(const std::vector<Input>& in, size_t threads, size_t& calls) {
-  std::vector<Result> res(in.size());
+static std::string run_all(const std::vector<Input>& in, size_t threads, size_t& calls, std::vector<Result>& res) {
+  res.assign(in.size(), Result());
   std::vector<std::thread> th;
   for (size_t t = 0; t < threads; t++)
     th.emplace_back([&, t] {
@@ -201,11 +231,11 @@ int main(int argc, char** argv) {
     ss >> hex >> mark;
     if (hex == "-") hex.clear();
     Input x;
-    x.kind = kind == "id" ? ID : kind == "nym" ? NYM : IPK;
+    x.kind = kind == "id" ? ID : kind == "nym" ? NYM : kind == "audit" ? AUDIT : IPK;
     x.bn = curve == "bn254";
     x.tile = mark == "tile";
     x.honest = x.tile || mark == "honest";
-    const bool known = (kind == "id" || kind == "nym" || kind == "ipk") && (x.bn || curve == "fp256bn") &&
+    const bool known = (kind == "id" || kind == "nym" || kind == "ipk" || kind == "audit") && (x.bn || curve == "fp256bn") &&
                        hex.size() % 2 == 0 && (mark.empty() || x.honest);
     CHECK(known);
     if (!known) continue;
@@ -214,8 +244,11 @@ int main(int argc, char** argv) {
   }
   CHECK(!in.empty());
   size_t calls = 0, calls4 = 0;
-  const std::string serial = run_all(in, 1, calls), threaded = run_all(in, 4, calls4);
+  std::vector<Result> res, res4;
+  const std::string serial = run_all(in, 1, calls, res), threaded = run_all(in, 4, calls4, res4);
   CHECK(serial == threaded && calls == calls4);
+  for (size_t i = 0; i < in.size(); i++)
+    if (in[i].kind == AUDIT) printf("audit %zu %d %d\n", i, res[i].pre, res[i].rh_pre);
   printf("idemix_parse_check: %zu inputs, %zu parser calls, sha256 %s\n", in.size(), calls, serial.c_str());
   if (g_failed) {
     fprintf(stderr, "idemix_parse_check: %d checks failed\n", g_failed.load());

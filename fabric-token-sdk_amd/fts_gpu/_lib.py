@@ -39,6 +39,13 @@ FTS_E_ID_REVOCATION = 23
 FTS_E_ID_APRIME = 24
 FTS_E_ID_PAIRING = 25
 FTS_E_ID_ZK = 26
+FTS_E_AUDIT_MALFORMED = 27
+FTS_E_AUDIT_NO_EIDNYM = 28
+FTS_E_AUDIT_EID_POINT = 29
+FTS_E_AUDIT_EID_MISMATCH = 30
+FTS_E_AUDIT_NO_RHNYM = 31
+FTS_E_AUDIT_RH_POINT = 32
+FTS_E_AUDIT_RH_MISMATCH = 33
 # mathlib CurveID of idemix issuer keys
 FTS_CURVE_FP256BN_AMCL = 0
 FTS_CURVE_BN254 = 1
@@ -63,6 +70,7 @@ EXPORTED = [
     "fts_nym_last_timings", "fts_idemix_idv_create", "fts_idemix_idv_destroy", "fts_idemix_identity_verify_batch",
     "fts_idemix_identity_last_timings", "fts_idemix_identity_last_stats", "fts_idemix_pairing_debug", "fts_ctx_create_opts", "fts_debug_hold",
     "fts_debug_dispatch_stats", "fts_debug_stage_actions",
+    "fts_idemix_audit_match_batch", "fts_idemix_audit_last_timings",
 ]
 
 
@@ -99,6 +107,11 @@ class EcdsaItem(C.Structure):
 class NymItem(C.Structure):
     _fields_ = [("nym", C.c_void_p), ("nym_len", C.c_size_t), ("sig", C.c_void_p), ("sig_len", C.c_size_t),
                 ("msg", C.c_void_p), ("msg_len", C.c_size_t)]
+
+
+class AuditItem(C.Structure):
+    _fields_ = [("id", C.c_void_p), ("id_len", C.c_size_t), ("eid", C.c_void_p), ("eid_len", C.c_size_t),
+                ("r_eid32", C.c_void_p), ("rh", C.c_void_p), ("rh_len", C.c_size_t), ("r_rh32", C.c_void_p)]
 
 
 class ActionWitness(C.Structure):
@@ -183,6 +196,8 @@ def _load():
         "fts_idemix_identity_last_timings": ([P, C.POINTER(C.c_float)], C.c_int),
         "fts_idemix_identity_last_stats": ([P, C.POINTER(C.c_uint32)], C.c_int),
         "fts_idemix_pairing_debug": ([P, C.c_int, U8P, C.c_int, C.POINTER(C.c_uint32)], C.c_int),
+        "fts_idemix_audit_match_batch": ([P, S, C.POINTER(AuditItem), I32P], C.c_int),
+        "fts_idemix_audit_last_timings": ([P, C.POINTER(C.c_float)], C.c_int),
     }
     for name, (args, res) in sig.items():
         try:

@@ -22,6 +22,8 @@ from . import _lib as L
 from ._lib import FTS_OK, FTS_E_NYM_MALFORMED, FTS_E_NYM_BADKEY, FTS_E_NYM_INVALID  # noqa: F401
 from ._lib import (FTS_E_ID_MALFORMED, FTS_E_ID_BADNYM, FTS_E_ID_NO_EIDNYM, FTS_E_ID_NO_RHNYM,  # noqa: F401
                    FTS_E_ID_REVOCATION, FTS_E_ID_APRIME, FTS_E_ID_PAIRING, FTS_E_ID_ZK)
+from ._lib import (FTS_E_AUDIT_MALFORMED, FTS_E_AUDIT_NO_EIDNYM, FTS_E_AUDIT_EID_POINT,  # noqa: F401
+                   FTS_E_AUDIT_EID_MISMATCH, FTS_E_AUDIT_NO_RHNYM, FTS_E_AUDIT_RH_POINT, FTS_E_AUDIT_RH_MISMATCH)
 from ._lib import FTS_CURVE_BN254, FTS_CURVE_FP256BN_AMCL  # noqa: F401
 
 
@@ -211,6 +213,48 @@ class IdentityVerifier:
         L.check("fts_idemix_identity_last_stats", L.lib.fts_idemix_identity_last_stats(self.h, out))
         return int(out[0]), int(out[1])
 
+    def audit_match_batch(self, identities, eids=(), r_eids=(), rhs=(), r_rhs=()):
+        """AuditInfo.Match (services/identity/idemix/crypto/audit.go:40-84) for n owner
+        identities in one device pass (fts_idemix_audit_match_batch): eids / rhs are
+        AuditInfo.Attributes[2] / [3], r_eids / r_rhs the 32-byte Rand.Bytes() of
+        EidNymAuditData / RhNymAuditData (None: a nil Rand).  The identity's proof is
+        not verified here (verify_batch).  -> int32 status array (FTS_OK or FTS_E_AUDIT_*)"""
+        n = len(identities)
+        if not (len(eids) == len(r_eids) == len(rhs) == len(r_rhs) == n):
+            raise ValueError("identities, eids, r_eids, rhs and r_rhs must have the same length")
+        st = np.zeros(n, dtype=np.int32)
+        if n == 0:
+            return st
+        for r in list(r_eids) + list(r_rhs):
+            if r is not None and len(r) != 32:
+                raise ValueError("a rand is 32 bytes (Zr.Bytes())")
+
+        def ptr(b):  # None: NULL; b"" keeps a valid pointer
+            return None if b is None else C.cast(C.c_char_p(b), C.c_void_p)
+        keep = [tuple(None if x is None else bytes(x) for x in t) for t in zip(identities, eids, r_eids, rhs, r_rhs)]
+        items = (L.AuditItem * n)()
+        for i, (ident, eid, r_eid, rh, r_rh) in enumerate(keep):
+            it = items[i]
+            it.id, it.id_len = ptr(ident), len(ident or b"")
+            it.eid, it.eid_len = ptr(eid), len(eid or b"")
+            it.rh, it.rh_len = ptr(rh), len(rh or b"")
+            it.r_eid32, it.r_rh32 = ptr(r_eid), ptr(r_rh)
+        L.check("fts_idemix_audit_match_batch",
+                L.lib.fts_idemix_audit_match_batch(self.h, n, items, st.ctypes.data_as(C.POINTER(C.c_int32))))
+        return st
+
+    def Match(self, identity, eid, r_eid, rh, r_rh):
+        """raises AuditMatchError with the reference's message, as AuditInfo.Match errors"""
+        st = int(self.audit_match_batch([identity], [eid], [r_eid], [rh], [r_rh])[0])
+        if st != FTS_OK:
+            raise AuditMatchError(message(st), st)
+
+    def last_audit_kernel_ms(self):
+        """HIP-event ms of the last audit_match_batch's kernel"""
+        ms = C.c_float()
+        L.check("fts_idemix_audit_last_timings", L.lib.fts_idemix_audit_last_timings(self.h, C.byref(ms)))
+        return ms.value
+
     def pairing_debug(self, which, p64, final_exp=True):
         """e(W or g2, P) (BN254 only): 6 Fp2 coefficients (w^0..w^5) as Montgomery ints"""
         out = (C.c_uint32 * 192)()
@@ -222,6 +266,12 @@ class IdentityVerifier:
 
 
 class IdentityError(Exception):
+    def __init__(self, msg, status):
+        super().__init__(msg)
+        self.status = status
+
+
+class AuditMatchError(Exception):
     def __init__(self, msg, status):
         super().__init__(msg)
         self.status = status

@@ -78,7 +78,17 @@ enum fts_status {
   FTS_E_ID_REVOCATION = 23, /* revocation algorithm other than ALG_NO_REVOCATION */
   FTS_E_ID_APRIME = 24,     /* "signature invalid: APrime = 1" */
   FTS_E_ID_PAIRING = 25,    /* "signature invalid: APrime and ABar don't have the expected structure" */
-  FTS_E_ID_ZK = 26          /* "signature invalid: zero-knowledge proof is invalid" */
+  FTS_E_ID_ZK = 26,         /* "signature invalid: zero-knowledge proof is invalid" */
+  /* idemix audit info against an owner identity (services/identity/idemix/crypto/audit.go:40-84
+     AuditInfo.Match -> IBM/idemix AuditNymEid / AuditNymRh), in the order checked: */
+  FTS_E_AUDIT_MALFORMED = 27,    /* SerializedIdemixIdentity or its Signature proto does not unmarshal,
+                                    empty proof, or a nil rand */
+  FTS_E_AUDIT_NO_EIDNYM = 28,    /* "no EidNym provided" */
+  FTS_E_AUDIT_EID_POINT = 29,    /* EidNym does not decode (G1FromProto) */
+  FTS_E_AUDIT_EID_MISMATCH = 30, /* "eid nym does not match" */
+  FTS_E_AUDIT_NO_RHNYM = 31,     /* "no RhNym provided" */
+  FTS_E_AUDIT_RH_POINT = 32,     /* RhNym does not decode */
+  FTS_E_AUDIT_RH_MISMATCH = 33   /* "rh nym does not match" */
 };
 
 /* ---- API return codes ---- */
@@ -471,6 +481,31 @@ int fts_idemix_identity_last_stats(fts_idemix_idv* idv, uint32_t* out);
  * after the final exponentiation (final_exp != 0) or the Miller value; out192 = 6 Fp2
  * coefficients of w^0..w^5, Montgomery, little-endian limbs. */
 int fts_idemix_pairing_debug(fts_idemix_idv* idv, int which, const uint8_t* p64, int final_exp, uint32_t* out192);
+
+/* ---- idemix audit info against owner identities ----
+ * Replaces AuditInfo.Match (services/identity/idemix/crypto/audit.go:40-84), which the
+ * auditor reaches through InspectIdentity for every output, input and issuer
+ * (crypto/audit/auditor.go:225-282): the two Csp.Verify calls with EidNymAuditOpts and
+ * RhNymAuditOpts, each recomputing HAttrs[idx] * HashToZr(attr) + HRand * rand and comparing
+ * it with the EidNym / RhNym point of the identity's proof (audit type AuditExpectSignature).
+ * The proof itself is NOT verified (that is fts_idemix_identity_verify_batch) and the nym
+ * public key is not read; the Signature proto must unmarshal as a whole.  The caller decodes
+ * the AuditInfo JSON and passes Attributes[2], Attributes[3] and the two Rand.Bytes(). */
+typedef struct {
+  const uint8_t* id;  size_t id_len;   /* SerializedIdemixIdentity (the token's Owner) */
+  const uint8_t* eid; size_t eid_len;  /* AuditInfo.Attributes[2] (may be empty) */
+  const uint8_t* r_eid32;              /* EidNymAuditData.Rand, Zr.Bytes(), 32 B BE (used mod r) */
+  const uint8_t* rh;  size_t rh_len;   /* AuditInfo.Attributes[3] */
+  const uint8_t* r_rh32;               /* RhNymAuditData.Rand */
+} fts_idemix_audit_item;
+/* status[i] <- FTS_OK or FTS_E_AUDIT_* (the first failing check: every EID check precedes
+ * every RH check; a NULL rand is FTS_E_AUDIT_MALFORMED).  FTS_API_EINVAL for a NULL handle,
+ * NULL arrays with n > 0, an attribute with a NULL pointer and a non-zero length or longer
+ * than 0xffffff00 bytes, or n above 2^22.  Thread-safe: up to 3 calls on one handle run
+ * concurrently on slots of their own, beside identity-verification calls. */
+int fts_idemix_audit_match_batch(fts_idemix_idv* idv, size_t n, const fts_idemix_audit_item* items, int32_t* status);
+/* HIP-event duration (ms) of the last batch's kernel (k_idv_audit). */
+int fts_idemix_audit_last_timings(fts_idemix_idv* idv, float* ms);
 
 #ifdef __cplusplus
 }
