@@ -115,7 +115,7 @@ static int ctx_create(const uint8_t* pp_bytes, size_t pp_len, uint32_t bits, int
     if (const char* e = getenv("FTS_WAVE_PRIO"))
       for (int i = 0; i < PS_N && e[i]; i++)
         if (e[i] >= '0' && e[i] <= '3') pr[i] = e[i] - '0';
-    if (rp_set_wave_prio(pr) != hipSuccess || msm_set_wave_prio(pr) != hipSuccess) return FTS_API_EDEVICE;
+    if (set_wave_prio(pr) != hipSuccess) return FTS_API_EDEVICE;
   }
   // the batch check's stream (s3: RLC weights + MSM, the longest chain of a small
   // pass) gets the device's highest stream priority, so its few waves are

@@ -397,7 +397,7 @@ static int rp_enqueue(fts_ctx* c, Lane& L, int B, uint8_t* d_raw, uint32_t* d_sc
   return FTS_API_OK;
 }
 
-// The single-fault locator (rp_kernels.hip k_rlc_locate): S' = (j + 1) S locates
+// The single-fault locator (rp_rlc.hip k_rlc_locate): S' = (j + 1) S locates
 // the one bad proof j of a failed combination S.  Its per-proof final equations
 // give its verdict (bulletproof.go:314-324, ipa.go:254-259), and every other proof
 // is accepted -- the combination of the others is S - rho_j E_j = 0 with the

@@ -26,7 +26,9 @@ FTS_DEV void wave_prio() {
   else if (p >= 3)
     __builtin_amdgcn_s_setprio(3);
 }
-// per translation unit (each holds its own copy of the table)
+// per translation unit (each holds its own copy of the table): a unit whose kernels call
+// wave_prio<>() exports a setter that calls this (declared in wave_prio.hpp), and
+// set_wave_prio (rp_pass.cpp) calls every unit's setter -- a new unit adds itself there
 static inline hipError_t upload_wave_prio(const int* p) {
   return hipMemcpyToSymbol(HIP_SYMBOL(g_wave_prio), p, sizeof(int) * PS_N, 0, hipMemcpyHostToDevice);
 }

@@ -23,9 +23,10 @@
 // Curves: BN254 (gnark; G1 64-byte raw encodings, 16-bit signed fixed-base
 // tables) and FP256BN (AMCL; 0x04 || X || Y, 16-bit unsigned tables), behind a
 // traits struct each.  Kernels, device tables and the launch_*<CV> templates only:
-// idemix_identity_bn.hip and idemix_identity_fbn.hip instantiate one curve each
-// (a curve's pairing kernels are minutes of device compilation; the two units
-// build in parallel), and the host code (api_idemix.cpp) sees device/launch.hpp.
+// idemix_identity_<cv>.hip, idemix_pairing_<cv>.hip and idemix_bp_<cv>.hip instantiate
+// one curve's launch sequences each (a curve's two pairing kernels are minutes of device
+// compilation each; the units build in parallel), and the host code (api_idemix.cpp)
+// sees device/launch.hpp.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -885,8 +886,8 @@ __global__ void __launch_bounds__(64) k_idv_pairing_debug(const uint32_t* __rest
 }
 
 // ------------------------------------------------- per-curve launch sequences
-// Declared in device/launch.hpp (with Chain); instantiated once per curve, each in
-// its own translation unit.
+// Declared in device/launch.hpp (with Chain); each instantiated once per curve, in one
+// of that curve's translation units.
 // decode, the t-value products, the t-values and the transcript
 template <class CV>
 void launch_tvals(const Chain& c) {

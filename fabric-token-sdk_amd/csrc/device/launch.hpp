@@ -26,11 +26,25 @@ struct Timeline;
 // "fb:" + nm, interned (Timeline marks after fallback())
 const char* fallback_name(const char* nm);
 
-// ---- rp_kernels.hip
+// thread-per-item launch: ceil(nthreads / bs) blocks of bs threads, nothing for zero items
+#define FTS_LAUNCH(kern, nthreads, bs, stream, ...)                                   \
+  do {                                                                                \
+    size_t nt_ = (size_t)(nthreads);                                                  \
+    if (nt_) hipLaunchKernelGGL(kern, dim3((unsigned)((nt_ + (bs)-1) / (bs))), dim3(bs), 0, stream, __VA_ARGS__); \
+  } while (0)
+
+// ---- rp_pass.cpp
 extern int g_lat_bs;                // block size of the latency-bound per-proof kernels
 extern std::atomic<int> g_work_bs;  // FTS_WORK_BS: written by context creation while other lanes launch
-size_t rp_scratch_words(int B, int n, int k);
-size_t rp_terms_words(int B, int n, int k);
+void launch_rp_batch(const RpBatchDev& d, const RlcDev& r, const uint32_t* tables, const uint32_t* wtables,
+                     const uint8_t* x0_const, const uint8_t* x0_tmpl, hipStream_t s, hipStream_t s2, hipStream_t s3,
+                     hipStream_t s4, Timeline* tl, int wbits);
+void launch_rp_gather(const RpGather& g, int k, uint8_t* raw, uint32_t* sc, int32_t* status, int32_t* ipa,
+                      hipStream_t s);
+// wave priority table (wave_prio.hpp PrioSlot) of every unit whose kernels call wave_prio<>()
+hipError_t set_wave_prio(const int* p);
+
+// ---- rp_tables.hip
 size_t fb_words_per_base();
 size_t fbw_words_per_base(int wbits);
 size_t table_build_scratch_bytes(int nb);
@@ -38,27 +52,31 @@ size_t wide_build_scratch_bytes(int nb, int wbits);
 void launch_build_tables(const uint32_t* bases, int nb, uint32_t* tables, uint32_t* scratch, hipStream_t s);
 void launch_build_wide_tables(const uint32_t* bases, int nb, uint32_t* tables, uint32_t* scratch, hipStream_t s,
                               int wbits);
-void launch_rp_batch(const RpBatchDev& d, const RlcDev& r, const uint32_t* tables, const uint32_t* wtables,
-                     const uint8_t* x0_const, const uint8_t* x0_tmpl, hipStream_t s, hipStream_t s2, hipStream_t s3,
-                     hipStream_t s4, Timeline* tl, int wbits);
-void launch_rp_fallback(const RpBatchDev& d, const uint32_t* tables, const int32_t* sel, int nsel, hipStream_t s,
-                        Timeline* tl);
+void launch_msm_gen_points(int N, const uint8_t* raw_k, const uint8_t* raw_s, const uint32_t* table, uint32_t* jac,
+                           uint32_t* pts, uint32_t* sc, hipStream_t s);
+
+// ---- rp_x0.hip
+void launch_normalize(size_t total, int per, int stride, int first, const int32_t* status, const uint32_t* jac,
+                      uint32_t* aff, uint8_t* be, hipStream_t s, uint8_t* x0msgs = nullptr);
+void launch_normalize_all(int total, const uint32_t* jac, uint32_t* aff, hipStream_t s);
+void launch_x0(int B, int n, int k, const int32_t* status, const uint8_t* hp_be, const uint8_t* x0_const,
+               const uint8_t* x0_tmpl, const uint32_t* sc, uint8_t* msgs, uint32_t* ch, hipStream_t s);
+
+// ---- rp_rlc.hip
+// column Q of the ungrouped combination (after x0): partial sums, their sum, its product -> r.fixed
+void launch_rlc_q_column(const RpBatchDev& d, const RlcDev& r, const uint32_t* tables, hipStream_t s, Timeline* tl);
 void launch_rlc_group_test(const RpBatchDev& d, const RlcDev& r, const uint32_t* tables, const MsmPlan& p,
                            const int32_t* sel, int G, int gs, uint32_t* gcol, uint32_t* gfix, int32_t* next,
                            uint32_t* next_count, hipStream_t s, Timeline* tl);
-void launch_rp_gather(const RpGather& g, int k, uint8_t* raw, uint32_t* sc, int32_t* status, int32_t* ipa,
-                      hipStream_t s);
 void launch_rlc_locate(const RpBatchDev& d, const RlcDev& r, const uint32_t* tables, uint32_t* save, int32_t* loc,
                        hipStream_t s, Timeline* tl);
 void launch_rlc_accept_except(int B, int skip, int32_t* status, const int32_t* ipa_flag, hipStream_t s);
-void launch_normalize_all(int total, const uint32_t* jac, uint32_t* aff, hipStream_t s);
-void launch_msm_gen_points(int N, const uint8_t* raw_k, const uint8_t* raw_s, const uint32_t* table, uint32_t* jac,
-                           uint32_t* pts, uint32_t* sc, hipStream_t s);
-void launch_x0(int B, int n, int k, const int32_t* status, const uint8_t* hp_be, const uint8_t* x0_const,
-               const uint8_t* x0_tmpl, const uint32_t* sc, uint8_t* msgs, uint32_t* ch, hipStream_t s);
-// wave priority table (helpers.hpp PrioSlot) of rp_kernels.hip's and msm.hip's kernels
-hipError_t rp_set_wave_prio(const int* p);
-hipError_t msm_set_wave_prio(const int* p);
+
+// ---- rp_fallback.hip
+size_t rp_scratch_words(int B, int n, int k);
+size_t rp_terms_words(int B, int n, int k);
+void launch_rp_fallback(const RpBatchDev& d, const uint32_t* tables, const int32_t* sel, int nsel, hipStream_t s,
+                        Timeline* tl);
 
 // ---- msm.hip
 // ev_stage (optional): recorded on s after the counting sort (stage 1) or the bucket
@@ -100,7 +118,7 @@ void launch_nym_verify(bool bn, int n, const uint32_t* rec, const uint8_t* nym, 
 
 }  // namespace fts
 
-// ---- idemix_identity_bn.hip, idemix_identity_fbn.hip (device/idv_kernels.hpp)
+// ---- idemix_identity_<cv>.hip, idemix_pairing_<cv>.hip, idemix_bp_<cv>.hip, cv = bn | fbn (device/idv_kernels.hpp)
 namespace idv {
 struct BnCurve;
 struct FbnCurve;
@@ -123,7 +141,7 @@ struct Chain {
   int32_t *gok, *cnt, *list;
   Key8 key;
 };
-// per curve, instantiated in that curve's unit
+// per curve, instantiated in that curve's units
 template <class CV>
 void launch_tvals(const Chain& c);
 template <class CV>

@@ -1,6 +1,8 @@
 // Wave-priority slots of the batch-verify pass's kernels (host and device; the
-// table and s_setprio helper live in helpers.hpp).
+// table and s_setprio helper live in helpers.hpp, one copy of the table per translation
+// unit).
 #pragma once
+#include <hip/hip_runtime.h>
 
 namespace fts {
 enum PrioSlot {
@@ -20,5 +22,13 @@ enum PrioSlot {
   PS_N
 };
 #define FTS_WAVE_PRIO_DEFAULT {0, 2, 2, 1, 1, 3, 3, 1, 3, 1, 3, 3}
+
+// Each unit whose kernels call wave_prio<>() uploads its own copy of the table
+// (helpers.hpp upload_wave_prio); set_wave_prio (launch.hpp, rp_pass.cpp) calls them all.
+// A new unit with prioritised kernels adds its setter here and to set_wave_prio.
+hipError_t upload_wave_prio_rp_exact(const int* p);
+hipError_t upload_wave_prio_rp_x0(const int* p);
+hipError_t upload_wave_prio_rp_rlc(const int* p);
+hipError_t upload_wave_prio_msm(const int* p);
 
 }  // namespace fts

@@ -5,7 +5,7 @@
 //
 // Host side of the drop-in boundary: context creation from the public
 // parameters (setup.go:319-372), DER decoding of proofs into device records,
-// orchestration of the HIP kernels in rp_kernels.hip / sigma_kernels.hip, and
+// orchestration of the HIP kernels in the rp_*.hip units / sigma_kernels.hip, and
 // the reference error-precedence rules (transfer.go:153-197,
 // issue/verifier.go:32-57, rangecorrectness.go:137-162).
 #pragma once
@@ -341,7 +341,7 @@ struct fts_ctx {
   // dispatcher counters (fts_debug_dispatch_stats)
   std::atomic<int64_t> st_passes{0}, st_reqs{0}, st_max_merged{0}, st_act_reqs{0};
   // passes of up to com_fixed_max proofs compute com on the latency path (fixed-base
-  // groups, rp_kernels.hip k_rp_fixed_all), larger ones on the work path (Horner +
+  // groups, rp_exact.hip k_rp_fixed_all), larger ones on the work path (Horner +
   // joint GLV chains): the same group element either way
   size_t com_fixed_max = 16384;
   // group test: round-1 group size and round-2 threshold (FTS_GT1 / FTS_GT2_MIN).  Larger

@@ -1,12 +1,11 @@
-// BN254 instances of the identity-proof kernels (device/idv_kernels.hpp), the two
-// BN254-only kernels and the size functions the host code needs.
+// BN254 instances of the identity-proof kernels (device/idv_kernels.hpp) but the pairing
+// ones (idemix_pairing_bn.hip, idemix_bp_bn.hip): the t-values and the line tables, the
+// BN254-only epoch-key check and the size functions the host code needs.
 #include "device/idv_kernels.hpp"
 
 namespace idv {
 
 template void launch_tvals<BnCurve>(const Chain&);
-template void launch_batch<BnCurve>(const Chain&);
-template void launch_pairing<BnCurve>(const Chain&, unsigned, bool);
 template void launch_lines<BnCurve>(const uint8_t*, uint32_t*, int32_t*, hipStream_t);
 
 // U distinct epoch keys (128 raw bytes each, BN254): ok[u] <- the key decodes (on the
@@ -27,10 +26,6 @@ __global__ void __launch_bounds__(64) k_idv_g2_check(int M, const int32_t* __res
 }
 void launch_g2_check(int M, const int32_t* idx, const uint8_t* keys, int32_t* ok, hipStream_t s) {
   k_idv_g2_check<<<(unsigned)((M + 63) / 64), 64, 0, s>>>(M, idx, keys, ok);
-}
-void launch_pairing_debug(const uint32_t* lines, int which, const uint32_t* p16, uint32_t* out, int final_exp,
-                          hipStream_t s) {
-  k_idv_pairing_debug<BnCurve><<<1, 64, 0, s>>>(lines, which, p16, out, final_exp);
 }
 
 size_t line_words(bool bn) {

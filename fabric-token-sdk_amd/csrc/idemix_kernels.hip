@@ -18,7 +18,7 @@
 //
 // Kernels (one signature per lane):
 //   (build once per issuer key)  16-bit fixed-base tables of HSk and HRand
-//       (rp_kernels.hip launch_build_tables, 32 MiB each)
+//       (rp_tables.hip launch_build_tables, 32 MiB each)
 //   k_nym_verify  nym decode + on-curve check, t = s_sk HSk + s_rnym HRand
 //       (2 x 16 mixed additions) + (r - c) Nym (GLV, glv.hpp), affine t,
 //       SHA-256 over the 164-byte prefix and the message (streamed from HBM

@@ -726,12 +726,6 @@ __global__ void k_msm_to_bytes(const uint32_t* __restrict__ jac, uint8_t* __rest
   store_point_be(out, g1j_to_affine(load_g1j(jac)));
 }
 
-#define FTS_LAUNCH(kern, nthreads, bs, stream, ...)                                   \
-  do {                                                                                \
-    size_t nt_ = (size_t)(nthreads);                                                  \
-    if (nt_) hipLaunchKernelGGL(kern, dim3((unsigned)((nt_ + (bs)-1) / (bs))), dim3(bs), 0, stream, __VA_ARGS__); \
-  } while (0)
-
 // scratch: NS * 24 words.  p.d_win must already hold p.win (uploaded by the caller).
 // `extra` (nextra Jacobian points) is produced on stream s_extra: joined
 // before the window reduction that sums it.
@@ -891,5 +885,5 @@ void launch_msm_to_bytes(const uint32_t* jac, uint8_t* out, hipStream_t s) {
   hipLaunchKernelGGL(k_msm_to_bytes, dim3(1), dim3(64), 0, s, jac, out);
 }
 
-hipError_t msm_set_wave_prio(const int* p) { return upload_wave_prio(p); }
+hipError_t upload_wave_prio_msm(const int* p) { return upload_wave_prio(p); }
 }  // namespace fts

@@ -232,13 +232,7 @@ __global__ void __launch_bounds__(64) k_sig_finish(int A, const SigAction* __res
   status[a] = eq ? FTS_OK : (ac.kind == SIG_TAS ? FTS_E_TAS_INVALID : FTS_E_ST_INVALID);
 }
 
-#define FTS_LAUNCH(kern, nthreads, bs, stream, ...)                                   \
-  do {                                                                                \
-    size_t nt_ = (size_t)(nthreads);                                                  \
-    if (nt_) hipLaunchKernelGGL(kern, dim3((unsigned)((nt_ + (bs)-1) / (bs))), dim3(bs), 0, stream, __VA_ARGS__); \
-  } while (0)
-
-// batch affine normalisation (rp_kernels.hip): all naff slots of the sigma batch
+// batch affine normalisation (rp_x0.hip): all naff slots of the sigma batch
 // phase 1 (before the range-proof batch): decode + primes (writes the rp V slots)
 void launch_sig_prep(const SigBatchDev& d, hipStream_t s) {
   FTS_LAUNCH(k_sig_decode, d.npts, 256, s, d.npts, d.raw, d.pt_owner, d.pts, d.status);

@@ -533,7 +533,7 @@ def test_idle_burst_splits_into_even_passes(pp_raw):
 
 @pytest.mark.gpu
 def test_single_fault_locator(pp_raw):
-    """api_rp.cpp rp_locate_single / rp_kernels.hip k_rlc_locate: a failed batch
+    """api_rp.cpp rp_locate_single / rp_rlc.hip k_rlc_locate: a failed batch
     check with ONE bad proof is decided by the index-weighted recombination
     (S' = (i + 1) S) and that proof's per-proof equations, without the group test;
     the other proofs' deferred IPA structural verdicts (a truncated IPA: "invalid
