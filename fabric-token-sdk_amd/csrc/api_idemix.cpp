@@ -630,12 +630,20 @@ int fts_idemix_audit_last_timings(fts_idemix_idv* K, float* ms) {
 
 int fts_idemix_pairing_debug(fts_idemix_idv* K, int which, const uint8_t* p64, int final_exp, uint32_t* out192) {
   if (!K || !p64 || !out192 || (which != 0 && which != 1)) return FTS_API_EINVAL;
-  // P: 64 raw BE bytes -> affine Montgomery on the host (BN254 only)
-  host::G1A a;
-  if (K->curve != FTS_CURVE_BN254 || !host::g1_from_bytes(p64, 64, a) || a.inf) return FTS_API_EINVAL;
+  // P: 64 raw BE bytes -> 16 words as base_words() hands points over: BN254 affine Montgomery
+  // (decoded and on-curve checked here), FP256BN canonical limbs < p (converted on the device)
+  const bool bn = K->curve == FTS_CURVE_BN254;
   uint32_t pm[16];
-  memcpy(pm, a.x.v, 32);
-  memcpy(pm + 8, a.y.v, 32);
+  if (bn) {
+    host::G1A a;
+    if (!host::g1_from_bytes(p64, 64, a) || a.inf) return FTS_API_EINVAL;
+    memcpy(pm, a.x.v, 32);
+    memcpy(pm + 8, a.y.v, 32);
+  } else {
+    u256::be_limbs(p64, 32, pm);
+    u256::be_limbs(p64 + 32, 32, pm + 8);
+    if (u256::ge(pm, u256::kPfbn) || u256::ge(pm + 8, u256::kPfbn)) return FTS_API_EINVAL;
+  }
   std::lock_guard<std::mutex> l(K->ring.mu);
   ICHK(hipSetDevice(K->device));
   // private stream and buffers, released on every exit path
@@ -649,7 +657,8 @@ int fts_idemix_pairing_debug(fts_idemix_idv* K, int which, const uint8_t* p64, i
   ICHK(r.s.create());
   if (!r.p.reserve(64) || !r.o.reserve(192 * 4)) return FTS_API_EDEVICE;
   ICHK(hipMemcpyAsync(r.p.p, pm, 64, hipMemcpyHostToDevice, r.s));
-  launch_pairing_debug(K->d_lines.as<uint32_t>(), which, r.p.as<uint32_t>(), r.o.as<uint32_t>(), final_exp, r.s);
+  if (bn) launch_pairing_debug<BnCurve>(K->d_lines.as<uint32_t>(), which, r.p.as<uint32_t>(), r.o.as<uint32_t>(), final_exp, r.s);
+  else launch_pairing_debug<FbnCurve>(K->d_lines.as<uint32_t>(), which, r.p.as<uint32_t>(), r.o.as<uint32_t>(), final_exp, r.s);
   ICHK(hipGetLastError());
   ICHK(hipMemcpyAsync(out192, r.o.p, 192 * 4, hipMemcpyDeviceToHost, r.s));
   ICHK(hipStreamSynchronize(r.s));

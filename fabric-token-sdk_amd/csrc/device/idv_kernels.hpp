@@ -74,6 +74,7 @@ struct BnCurve {
   using F = Fp;
   using PJ = G1J;
   static constexpr int G1_BYTES = 64;
+  static constexpr bool HOST_MONT = true;  // the host hands points over in Montgomery form (host/bn254_host.hpp)
   static FTS_DEV PJ inf() { return g1j_identity(); }
   static FTS_DEV bool is_inf(const PJ& p) { return f_is_zero(p.z); }
   static FTS_DEV PJ dbl(const PJ& p) { return g1j_dbl(p); }
@@ -130,6 +131,7 @@ struct FbnCurve {
   using F = fbn::Fp;
   using PJ = fbn::PJ;
   static constexpr int G1_BYTES = 65;
+  static constexpr bool HOST_MONT = false;  // the host hands over plain LE limbs (no Montgomery code for this p there)
   static FTS_DEV PJ inf() { return fbn::pj_inf(); }
   static FTS_DEV bool is_inf(const PJ& p) { return fbn::is_zero(p.z); }
   static FTS_DEV PJ dbl(const PJ& p) { return fbn::pj_dbl(p); }
@@ -866,8 +868,9 @@ __global__ void __launch_bounds__(256) k_idv_bp_sel(int n, const int32_t* __rest
   list[atomicAdd(count, 1)] = i;
 }
 
-// debug: e(Q, P) for Q = W (which 0) or g2 (1), P affine Montgomery -> GT (12 Fp2
-// coefficients w^0..w^5 as (c0.c0, c1.c0, c0.c1, c1.c1, c0.c2, c1.c2), plain LE limbs)
+// debug: e(Q, P) for Q = W (which 0) or g2 (1), P affine as the curve's host hands it over
+// (CV::HOST_MONT: Montgomery, else canonical limbs < p, converted here) -> GT (12 Fp2
+// coefficients w^0..w^5 as (c0.c0, c1.c0, c0.c1, c1.c1, c0.c2, c1.c2), Montgomery LE limbs)
 template <class CV>
 __global__ void __launch_bounds__(64) k_idv_pairing_debug(const uint32_t* __restrict__ lines, int which, const uint32_t* __restrict__ p16,
                                     uint32_t* __restrict__ out, int final_exp) {
@@ -876,7 +879,8 @@ __global__ void __launch_bounds__(64) k_idv_pairing_debug(const uint32_t* __rest
   using F = typename B::F;
   if (threadIdx.x) return;
   const uint32_t* const L[1] = {lines + (size_t)which * pair::n_lines<K>() * pair::LINE_WORDS};
-  const F xP[1] = {B::ld(p16)}, yP[1] = {B::ld(p16 + 8)};
+  F xP[1] = {B::ld(p16)}, yP[1] = {B::ld(p16 + 8)};
+  if constexpr (!CV::HOST_MONT) xP[0] = p256::to_mont(xP[0]), yP[0] = p256::to_mont(yP[0]);
   pair::F12<B> f = pair::miller<B, 1>(L, xP, yP);
   if (final_exp) f = pair::final_exp_i(f);
   const pair::F2<B> z[6] = {f.c0.c0, f.c1.c0, f.c0.c1, f.c1.c1, f.c0.c2, f.c1.c2};
@@ -914,6 +918,11 @@ void launch_pairing(const Chain& c, unsigned lanes, bool list) {
 template <class CV>
 void launch_lines(const uint8_t* w, uint32_t* lines, int32_t* ok, hipStream_t s) {
   k_idv_lines<CV><<<1, 64, 0, s>>>(w, lines, ok);
+}
+template <class CV>
+void launch_pairing_debug(const uint32_t* lines, int which, const uint32_t* p16, uint32_t* out, int final_exp,
+                          hipStream_t s) {
+  k_idv_pairing_debug<CV><<<1, 64, 0, s>>>(lines, which, p16, out, final_exp);
 }
 
 }  // namespace idv

@@ -150,10 +150,12 @@ template <class CV>
 void launch_pairing(const Chain& c, unsigned lanes, bool list);
 template <class CV>
 void launch_lines(const uint8_t* w, uint32_t* lines, int32_t* ok, hipStream_t s);
-// BN254 only
-void launch_g2_check(int M, const int32_t* idx, const uint8_t* keys, int32_t* ok, hipStream_t s);
+// debug pairing; p16: affine P as 16 words, BN254 Montgomery / FP256BN canonical limbs < p
+template <class CV>
 void launch_pairing_debug(const uint32_t* lines, int which, const uint32_t* p16, uint32_t* out, int final_exp,
                           hipStream_t s);
+// BN254 only
+void launch_g2_check(int M, const int32_t* idx, const uint8_t* keys, int32_t* ok, hipStream_t s);
 // sizes (words): pairing lines per G2 point, the t-value kernels' scratch, the batch check's layout in it
 size_t line_words(bool bn);
 size_t idv_scratch_words(size_t n);

@@ -14,6 +14,10 @@ constexpr uint32_t kRbn[8] = {0xf0000001u, 0x43e1f593u, 0x79b97091u, 0x2833e848u
 constexpr uint32_t kRfbn[8] = {0xd10b500du, 0xf62d536cu, 0x1299921au, 0x0cdc65fbu,
                                0xee71a49eu, 0x46e5f25eu, 0xfffcf0cdu, 0xffffffffu};
 
+// field prime of FP256BN
+constexpr uint32_t kPfbn[8] = {0xaed33013u, 0xd3292ddbu, 0x12980a82u, 0x0cdc65fbu,
+                               0xee71a49fu, 0x46e5f25eu, 0xfffcf0cdu, 0xffffffffu};
+
 inline bool ge(const uint32_t a[8], const uint32_t m[8]) {
   for (int k = 7; k >= 0; k--)
     if (a[k] != m[k]) return a[k] > m[k];

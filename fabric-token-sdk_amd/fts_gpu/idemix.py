@@ -256,7 +256,8 @@ class IdentityVerifier:
         return ms.value
 
     def pairing_debug(self, which, p64, final_exp=True):
-        """e(W or g2, P) (BN254 only): 6 Fp2 coefficients (w^0..w^5) as Montgomery ints"""
+        """e(W or g2, P) on the handle's curve, P = X || Y (64 raw BE bytes): 6 Fp2
+        coefficients (w^0..w^5) as Montgomery ints"""
         out = (C.c_uint32 * 192)()
         L.check("fts_idemix_pairing_debug",
                 L.lib.fts_idemix_pairing_debug(self.h, int(which), bytes(p64), int(bool(final_exp)), out))

@@ -477,9 +477,11 @@ int fts_idemix_identity_last_timings(fts_idemix_idv* idv, float* ms);
  * randomised pairing product each (0 with FTS_IDV_BATCH=0), out[1] = identities paired one
  * by one (those of the groups whose product was not 1; every identity with the batch off). */
 int fts_idemix_identity_last_stats(fts_idemix_idv* idv, uint32_t* out);
-/* Debug (tests): e(Q, P) for Q = W (which 0) or g2 (1) and P = 64 raw BE bytes (BN254),
- * after the final exponentiation (final_exp != 0) or the Miller value; out192 = 6 Fp2
- * coefficients of w^0..w^5, Montgomery, little-endian limbs. */
+/* Debug (tests): e(Q, P) on the handle's curve (BN254 or FP256BN) for Q = W (which 0) or
+ * g2 (1) and P = X || Y, 64 raw BE bytes (FP256BN too: no 0x04 prefix), after the final
+ * exponentiation (final_exp != 0) or the Miller value; out192 = 6 Fp2 coefficients of
+ * w^0..w^5, Montgomery, little-endian limbs.  BN254: P must decode as a G1 point other than
+ * the identity; FP256BN: coordinates below p (curve membership is the caller's business). */
 int fts_idemix_pairing_debug(fts_idemix_idv* idv, int which, const uint8_t* p64, int final_exp, uint32_t* out192);
 
 /* ---- idemix audit info against owner identities ----

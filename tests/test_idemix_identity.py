@@ -78,19 +78,30 @@ def test_single_identity_api(verifiers, tag):
 def test_device_pairing_equals_oracle_gt(verifiers):
     """e(W, P) and e(g2, P) from the device (after the final exponentiation) equal
     the oracle's optimal ate values coefficient for coefficient (BN254)"""
+    _pairing_equals_oracle(verifiers["bn254"], "bn254", "bn254_charlie")
+
+
+def test_device_pairing_equals_oracle_gt_fp256bn(verifiers):
+    """the same on FP256BN (M-type twist, negative u, the full-width field) under the
+    fp256bn_validator issuer key: Miller value and GT element, which 0 and 1"""
+    _pairing_equals_oracle(verifiers["fp256bn"], "fp256bn", "fp256bn_validator")
+
+
+def _pairing_equals_oracle(verifier, tag, issuer):
     from oracle import idemix as OI, idemix_identity as ID, pairing as PR, pairing_tower as PT
-    PC, C = PR.BN254, OI.BN254C
+    PC, C = (PR.BN254, OI.BN254C) if tag == "bn254" else (PR.FP256BN, OI.FP256BNC)
     T = PT.Tower(PC)
-    W = ID.ipk_w(PC, _ipk("bn254_charlie"))
+    W = ID.ipk_w(PC, _ipk(issuer))
     P = C.mul((1, 2), 123456789)
+    p64 = P[0].to_bytes(32, "big") + P[1].to_bytes(32, "big")
     R = 1 << 256
     for which, Q in ((0, W), (1, PC.g2_gen)):
-        dev = verifiers["bn254"].pairing_debug(which, C.g1_bytes(P))
+        dev = verifier.pairing_debug(which, p64)
         want = T._zs(T.final_exp(T.miller([(T.lines(Q), P)])))
         got = [((a * pow(R, -1, PC.p)) % PC.p, (b * pow(R, -1, PC.p)) % PC.p) for a, b in dev]
         assert got == [tuple(z) for z in want], which
         # Miller value too (before the final exponentiation): same algorithm step for step
-        devm = verifiers["bn254"].pairing_debug(which, C.g1_bytes(P), final_exp=False)
+        devm = verifier.pairing_debug(which, p64, final_exp=False)
         wantm = T._zs(T.miller([(T.lines(Q), P)]))
         gotm = [((a * pow(R, -1, PC.p)) % PC.p, (b * pow(R, -1, PC.p)) % PC.p) for a, b in devm]
         assert gotm == [tuple(z) for z in wantm], which
