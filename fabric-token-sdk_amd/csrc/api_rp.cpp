@@ -242,6 +242,7 @@ static int rp_group_fallback(fts_ctx* c, Lane& L, const RpBatchDev& d, const Rlc
   // left many proofs in large groups (the per-proof check's latency is one GLV
   // chain whatever their number, its work grows with it)
   if (sel_big.empty() || nfail <= RP_GT2_MIN) {
+    c->st_rp_perproof += nfail;
     launch_rp_fallback(d, c->d_tables.as<uint32_t>(), nxt, nfail, L.s, &L.tl);
     HIP_OK(hipGetLastError());
     return FTS_API_OK;
@@ -257,6 +258,7 @@ static int rp_group_fallback(fts_ctx* c, Lane& L, const RpBatchDev& d, const Rlc
   HIP_OK(L.sync());
   const int nfail2 = L.pin->flag;
   if (nfail2 == 0) return FTS_API_OK;
+  c->st_rp_perproof += nfail2;
   launch_rp_fallback(d, c->d_tables.as<uint32_t>(), nxt, nfail2, L.s, &L.tl);
   HIP_OK(hipGetLastError());
   return FTS_API_OK;
@@ -417,6 +419,7 @@ static int rp_locate_single(fts_ctx* c, Lane& L, RpPass& P) {
   HIP_OK(L.sync());
   const int i = L.pin->flag;
   if (i < 0 || i >= B) return 0;
+  c->st_rp_perproof += 1;
   launch_rp_fallback(P.d, c->d_tables.as<uint32_t>(), loc, 1, L.s, &L.tl);
   HIP_OK(hipGetLastError());
   HIP_OK(hipMemcpyAsync(&L.pin->flag, P.d.status + i, 4, hipMemcpyDeviceToHost, L.s));
@@ -424,6 +427,7 @@ static int rp_locate_single(fts_ctx* c, Lane& L, RpPass& P) {
   if (L.pin->flag == FTS_OK) return 0;  // not a fault after all: the group test decides
   launch_rlc_accept_except(B, i, P.d.status, P.d.ipa_flag, L.s);
   HIP_OK(hipGetLastError());
+  c->st_rp_located++;
   std::fill(P.dense.begin(), P.dense.end(), 0);
   return 1;
 }
@@ -437,9 +441,10 @@ static int rp_finish(fts_ctx* c, Lane& L, RpPass& P) {
   L.host_enqueue_ms = (float)(P.t_enq - P.t_prep);
   L.host_wait_ms = (float)(t_wait - P.t_enq);
   const int32_t flag = L.pin->flag;
-  c->last_fallback = flag ? 0 : 1;
+  c->st_rp_passes++;
   P.clean = flag != 0;
   if (flag) return FTS_API_OK;
+  c->st_rp_failed++;
   if (P.r.G > 1) {  // per-caller-batch combination: only the failing batches go to the group test
     std::vector<uint8_t> only((size_t)P.r.G, 0);
     for (int q = 0; q < P.r.G; q++) only[q] = L.pin->gflag[q] ? 0 : 1;
@@ -922,6 +927,20 @@ int fts_debug_dispatch_stats(const fts_ctx* c, int64_t* out) {
   out[1] = c->st_reqs.load();
   out[2] = c->st_max_merged.load();
   out[3] = c->st_act_reqs.load();
+  return FTS_API_OK;
+}
+
+int fts_debug_pass_stats(const fts_ctx* c, int64_t out[4]) {
+  if (!c || !out) return FTS_API_EINVAL;
+  out[0] = c->st_rp_passes.load();
+  out[1] = c->st_rp_failed.load();
+  out[2] = c->st_rp_located.load();
+  out[3] = c->st_rp_perproof.load();
+  for (const fts_ctx* ch : c->shards) {
+    int64_t o[4];
+    if (int rc = fts_debug_pass_stats(ch, o)) return rc;
+    for (int q = 0; q < 4; q++) out[q] += o[q];
+  }
   return FTS_API_OK;
 }
 

@@ -302,7 +302,6 @@ struct fts_ctx {
   // timings of the most recently completed range-proof run
   std::mutex tim_mu;
   TimingRecord tim;
-  std::atomic<int> last_fallback{0};
   // batch coalescing (fts_rp_batch_verify): staged batches submitted
   // concurrently are merged into one device pass of up to coalesce_max proofs
   std::deque<RpReq*> rp_pending;
@@ -340,6 +339,9 @@ struct fts_ctx {
   int hold_n = 0;
   // dispatcher counters (fts_debug_dispatch_stats)
   std::atomic<int64_t> st_passes{0}, st_reqs{0}, st_max_merged{0}, st_act_reqs{0};
+  // range-proof pass counters (fts_debug_pass_stats): passes finished, passes whose
+  // combination did not close, locator hits, proofs given to the per-proof equations
+  std::atomic<int64_t> st_rp_passes{0}, st_rp_failed{0}, st_rp_located{0}, st_rp_perproof{0};
   // passes of up to com_fixed_max proofs compute com on the latency path (fixed-base
   // groups, rp_exact.hip k_rp_fixed_all), larger ones on the work path (Horner +
   // joint GLV chains): the same group element either way

@@ -156,6 +156,13 @@ class PublicParams:
         L.check("fts_debug_dispatch_stats", L.lib.fts_debug_dispatch_stats(self._ctx, out))
         return tuple(out)
 
+    def pass_stats(self):
+        """(range-proof passes, passes whose combination did not close, locator hits,
+        proofs given to the per-proof equations) since creation (fts_debug_pass_stats)"""
+        out = (C.c_int64 * 4)()
+        L.check("fts_debug_pass_stats", L.lib.fts_debug_pass_stats(self._ctx, out))
+        return tuple(out)
+
     def reserve(self, max_pass_proofs=0):
         """pre-allocate every device lane for passes of up to max_pass_proofs
         (0: the coalescing cap) -- no allocation once batches flow"""

@@ -249,6 +249,13 @@ int fts_debug_stage_actions(fts_ctx* ctx, size_t n_tr, const fts_transfer_item* 
 /* dispatcher counters since context creation: out[0] device passes, out[1] calls served,
  * out[2] most calls in one pass, out[3] action calls (transfer / issue / actions / request) */
 int fts_debug_dispatch_stats(const fts_ctx* ctx, int64_t* out);
+/* range-proof pass counters since context creation, summed over the devices of a
+ * multi-device context: out[0] passes finished, out[1] passes whose batch check's
+ * combination did not close (a fallback decided them), out[2] single-fault locator
+ * hits, out[3] proofs handed to the per-proof final equations.  An honest pass adds
+ * (1, 0, 0, 0): a fallback gives the right verdicts whatever the main path computed,
+ * so only out[1] shows that the main path is sound. */
+int fts_debug_pass_stats(const fts_ctx* ctx, int64_t out[4]);
 /* per-kernel device time (ms) and algorithmic u32 MADs of b's last verification */
 int fts_rp_batch_timings(const fts_rp_batch* b, const char** names, float* ms, double* mads, int cap);
 void fts_rp_batch_free(fts_rp_batch* b);

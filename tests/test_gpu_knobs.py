@@ -213,9 +213,12 @@ def test_knob_msm_sort(pp_raw, sort):
         # an honest batch closes the combination with either sort (no fallback)
         vals = list(range(1, 769))
         proofs, coms = pp.prove_range_batch_gpu(vals, [(7).to_bytes(32, "big")] * 768, seed=0x50A8)
+        s0 = pp.pass_stats()
         st = pp.verify_range_proofs(proofs, coms)
         assert not any(int(s) for s in st)
         assert not any(k.startswith("fb:") for k in pp.last_timings()), sorted(pp.last_timings())
+        # the counter, which no timeline capacity cuts short (tests/test_gpu_clean_close.py)
+        assert tuple(a - b for a, b in zip(pp.pass_stats(), s0)) == (1, 0, 0, 0)
         b.close()
     finally:
         pp.close()
