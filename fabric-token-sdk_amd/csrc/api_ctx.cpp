@@ -27,6 +27,13 @@ HostPool& HostPool::get() {
 void host_parallel_for(size_t n, const std::function<void(size_t)>& f) { parallel_for(n, 2, f); }
 }  // namespace fts
 
+// the process's one table cache (host/table_cache.hpp); never destroyed, like the host
+// pool.  Its entries are owned by the contexts, not by it.
+DevTableCache& table_cache() {
+  static DevTableCache* t = new DevTableCache();
+  return *t;
+}
+
 namespace fts {
 namespace host {
 void build_prover_tables(const PublicParams& pp, int n, ProverTables& t) {
@@ -152,18 +159,45 @@ static int ctx_create(const uint8_t* pp_bytes, size_t pp_len, uint32_t bits, int
       memcpy(&hb[b * 16], bases[b].x.v, 32);  // 4x64 LE == 8x32 LE Montgomery form
       memcpy(&hb[b * 16 + 8], bases[b].y.v, 32);
     }
-  // build temporaries: s0 is drained before any exit below releases them
-  DevBuf bases_buf, scr_buf;
+  // The tables come from the device's table cache (host/table_cache.hpp, DESIGN.md
+  // §4.1): built by this call only when no live context on the device has the same
+  // bases at the same width.  FTS_TABLE_SHARE=0: private tables, as before the cache.
+  bool share = true;
+  if (const char* e = getenv("FTS_TABLE_SHARE")) share = atoi(e) != 0;
+  DevTableCache& cache = table_cache();
+  int build_rc = FTS_API_OK;  // why a build step failed (the cache reports only that it did)
+  const auto take = [&](const TableKey& key, size_t bytes, const std::function<bool(void*)>& build, TableRef& ref) {
+    bool built = true;
+    ref.e = share ? cache.acquire(key, bytes, build, &built) : cache.make_private(key, bytes, build);
+    ref.built = built;
+    return ref.e != nullptr;
+  };
+  // A build step uploads the bases, fills the entry's buffer on s0 and drains s0 before
+  // it returns: the entry is published (visible to other contexts' streams) only after
+  // that host-side synchronisation, and the step's temporaries go after it too.
   c->table_bytes = (size_t)nb * fb_words_per_base() * 4;
-  const int chunk = std::min(nb, 16);  // bases per build pass (bounds the Jacobian scratch)
-  if (!c->d_tables.reserve(c->table_bytes) || !bases_buf.reserve(hb.size() * 4) ||
-      !scr_buf.reserve(table_build_scratch_bytes(chunk)))
-    return FTS_API_ENOMEM;
-  uint32_t* const d_bases = bases_buf.as<uint32_t>();
-  hipMemcpyAsync(d_bases, hb.data(), hb.size() * 4, hipMemcpyHostToDevice, s0);
-  for (int b0 = 0; b0 < nb; b0 += chunk)
-    launch_build_tables(d_bases + (size_t)b0 * 16, std::min(chunk, nb - b0),
-                        c->d_tables.as<uint32_t>() + (size_t)b0 * fb_words_per_base(), scr_buf.as<uint32_t>(), s0);
+  const auto build_narrow = [&](void* p) {
+    DevBuf bases_buf, scr_buf;
+    const int chunk = std::min(nb, 16);  // bases per build pass (bounds the Jacobian scratch)
+    if (!bases_buf.reserve(hb.size() * 4) || !scr_buf.reserve(table_build_scratch_bytes(chunk))) {
+      (void)hipGetLastError();
+      build_rc = FTS_API_ENOMEM;
+      return false;
+    }
+    uint32_t* const d_bases = bases_buf.as<uint32_t>();
+    hipMemcpyAsync(d_bases, hb.data(), hb.size() * 4, hipMemcpyHostToDevice, s0);
+    for (int b0 = 0; b0 < nb; b0 += chunk)
+      launch_build_tables(d_bases + (size_t)b0 * 16, std::min(chunk, nb - b0),
+                          static_cast<uint32_t*>(p) + (size_t)b0 * fb_words_per_base(), scr_buf.as<uint32_t>(), s0);
+    if (hipStreamSynchronize(s0) != hipSuccess) {
+      build_rc = FTS_API_EDEVICE;
+      return false;
+    }
+    return true;
+  };
+  const int narrow_bits = 16;  // FB_W (device/fixed_base.hpp): the narrow set has one width
+  if (!take(TableKey::of(device, narrow_bits, hb.data(), nb), c->table_bytes, build_narrow, c->d_tables))
+    return build_rc != FTS_API_OK ? build_rc : FTS_API_ENOMEM;
   // wide tables of the per-proof bases H_i, K, P (same build, wider windows):
   // 22-bit windows (one mixed addition fewer per product: -8 % of the pass's
   // largest kernel) when the free HBM holds them with room to spare for the lanes'
@@ -172,12 +206,22 @@ static int ctx_create(const uint8_t* pp_bytes, size_t pp_len, uint32_t bits, int
   // fails, 20-bit
   {
     const int nw = n + 2;
+    std::vector<uint32_t> hw((size_t)nw * 16, 0);
+    for (int i = 0; i < nw; i++) {
+      const int src = i < n ? n + i : (i == n ? 2 * n + 4 : 2 * n + 2);  // H_i, K, P in `bases`
+      memcpy(&hw[(size_t)i * 16], &hb[(size_t)src * 16], 64);
+    }
+    // the wide key leaves the Pedersen generators out: public parameters that differ
+    // only in them share this set
+    const auto wide_key = [&](int wbits) { return TableKey::of(device, wbits, hw.data(), nw); };
     {
       // explicit width (fts_ctx_opts.wide_bits, else FTS_WIDE_BITS), else the budget:
       // 22-bit only when the whole context's tables fit the caller's table_budget
-      // (fts_ctx_opts) or, without one, when the free HBM keeps every lane's
-      // workspace (~8 GiB each for 81,920-proof passes at n = 64) and 128 GiB for
-      // other contexts and processes on the device
+      // (fts_ctx_opts, counted against the bytes the context reads, shared or not) or,
+      // without one, when a live context on the device already has (or is building)
+      // these bases' 22-bit set -- sharing it costs nothing -- or when the free HBM
+      // keeps every lane's workspace (~8 GiB each for 81,920-proof passes at n = 64)
+      // and 128 GiB for other contexts and processes on the device
       int wb = 20, forced = 0;
       if (opts && (opts->wide_bits == 20 || opts->wide_bits == 22)) {
         wb = opts->wide_bits, forced = 1;
@@ -188,6 +232,8 @@ static int ctx_create(const uint8_t* pp_bytes, size_t pp_len, uint32_t bits, int
         const size_t need22 = (size_t)nw * fbw_words_per_base(22) * 4;
         if (opts && opts->table_budget) {
           if (c->table_bytes + need22 <= opts->table_budget) wb = 22;
+        } else if (share && cache.has(wide_key(22))) {
+          wb = 22;
         } else if (hipMemGetInfo(&fr, &tot) == hipSuccess &&
                    fr > need22 + (size_t)nl * ((size_t)8 << 30) + ((size_t)128 << 30)) {
           wb = 22;
@@ -196,36 +242,37 @@ static int ctx_create(const uint8_t* pp_bytes, size_t pp_len, uint32_t bits, int
       c->wbits = wb;
       c->wbits_forced = forced;
     }
-    std::vector<uint32_t> hw((size_t)nw * 16, 0);
-    for (int i = 0; i < nw; i++) {
-      const int src = i < n ? n + i : (i == n ? 2 * n + 4 : 2 * n + 2);  // H_i, K, P in `bases`
-      memcpy(&hw[(size_t)i * 16], &hb[(size_t)src * 16], 64);
-    }
-    DevBuf wb_buf, wscr_buf;
-    int wchunk = 1;
-    for (;;) {  // 22-bit tables that do not fit after all (other contexts' lanes): 20-bit
-      wchunk = std::min(nw, c->wbits == 22 ? 1 : 4);  // bounds the Jacobian build scratch (2.4 / 1.6 GB)
-      if (c->d_wtables.reserve((size_t)nw * fbw_words_per_base(c->wbits) * 4) && wb_buf.reserve(hw.size() * 4) &&
-          wscr_buf.reserve(wide_build_scratch_bytes(wchunk, c->wbits)))
-        break;
-      wb_buf.release();
-      c->d_wtables.release();
-      (void)hipGetLastError();
+    const auto build_wide = [&](void* p) {
+      DevBuf wb_buf, wscr_buf;
+      const int wchunk = std::min(nw, c->wbits == 22 ? 1 : 4);  // bounds the Jacobian build scratch (2.4 / 1.6 GB)
+      if (!wb_buf.reserve(hw.size() * 4) || !wscr_buf.reserve(wide_build_scratch_bytes(wchunk, c->wbits))) {
+        (void)hipGetLastError();
+        build_rc = FTS_API_ENOMEM;
+        return false;
+      }
+      uint32_t* const d_wb = wb_buf.as<uint32_t>();
+      hipMemcpyAsync(d_wb, hw.data(), hw.size() * 4, hipMemcpyHostToDevice, s0);
+      for (int b0 = 0; b0 < nw; b0 += wchunk)
+        launch_build_wide_tables(d_wb + (size_t)b0 * 16, std::min(wchunk, nw - b0),
+                                 static_cast<uint32_t*>(p) + (size_t)b0 * fbw_words_per_base(c->wbits),
+                                 wscr_buf.as<uint32_t>(), s0, c->wbits);
+      if (hipStreamSynchronize(s0) != hipSuccess) {
+        build_rc = FTS_API_EDEVICE;
+        return false;
+      }
+      return true;
+    };
+    for (;;) {  // 22-bit tables that do not fit after all (other contexts' lanes): 20-bit, which may be a hit
+      build_rc = FTS_API_OK;
+      if (take(wide_key(c->wbits), (size_t)nw * fbw_words_per_base(c->wbits) * 4, build_wide, c->d_wtables)) break;
+      if (build_rc == FTS_API_EDEVICE) return FTS_API_EDEVICE;
       if (c->wbits == 22 && !c->wbits_forced) {
         c->wbits = 20;
         continue;
       }
-      (void)hipStreamSynchronize(s0);
       return FTS_API_ENOMEM;
     }
-    uint32_t* const d_wb = wb_buf.as<uint32_t>();
-    hipMemcpyAsync(d_wb, hw.data(), hw.size() * 4, hipMemcpyHostToDevice, s0);
-    for (int b0 = 0; b0 < nw; b0 += wchunk)
-      launch_build_wide_tables(d_wb + (size_t)b0 * 16, std::min(wchunk, nw - b0),
-                               c->d_wtables.as<uint32_t>() + (size_t)b0 * fbw_words_per_base(c->wbits),
-                               wscr_buf.as<uint32_t>(), s0, c->wbits);
     c->table_bytes += (size_t)nw * fbw_words_per_base(c->wbits) * 4;
-    if (hipStreamSynchronize(s0) != hipSuccess) return FTS_API_EDEVICE;
   }
   // constant part of the x0 transcript: hex(G_i) "||" ... hex(Q) "||"
   std::string xc;
@@ -253,8 +300,8 @@ static int ctx_create(const uint8_t* pp_bytes, size_t pp_len, uint32_t bits, int
 
 // ------------------------------------------------------ multi-device layer
 // A context over several devices (fts_ctx_create_devices / _mask) owns one
-// child context per device -- its own fixed-base tables, lanes, streams and
-// workspace -- and parses the public parameters itself as a host-only context
+// child context per device -- its own lanes, streams and workspace, and the
+// device's fixed-base tables (shared by the children on one device) -- and parses the public parameters itself as a host-only context
 // (host provers, commitments).  Each batch entry point splits the caller's
 // batch into contiguous shards balanced by a cost weight (fts_shard_plan),
 // runs shard j on child j from its own host thread, and lets every child write
@@ -294,7 +341,9 @@ int fts_ctx_create_devices(const uint8_t* pp, size_t pp_len, uint32_t bit_length
   if (rc != FTS_API_OK) return rc;
   c->shards.assign(ndev, nullptr);
   std::vector<int> crc(ndev, FTS_API_OK);
-  std::vector<std::thread> th;  // tables of every device built concurrently
+  // tables of every device built concurrently; shards on one device build each key once
+  // and wait for it (the table cache's single flight)
+  std::vector<std::thread> th;
   for (int j = 0; j < ndev; j++)
     th.emplace_back([&, j]() { crc[j] = fts_ctx_create_bits(pp, pp_len, bit_length, devices[j], &c->shards[j]); });
   for (auto& t : th) t.join();
@@ -359,6 +408,29 @@ int fts_ctx_info(const fts_ctx* c, fts_pp_info* o) {
   o->table_bytes = c->table_bytes;
   o->wide_bits = (uint32_t)c->wbits;
   o->lanes = (uint32_t)c->nlanes;
+  return FTS_API_OK;
+}
+
+int fts_ctx_table_info(const fts_ctx* c, int shard, fts_table_info* o) {
+  if (!c || !o) return FTS_API_EINVAL;
+  if (!c->shards.empty()) {
+    if (shard < 0 || shard >= (int)c->shards.size()) return FTS_API_EINVAL;
+    return fts_ctx_table_info(c->shards[shard], 0, o);
+  }
+  if (shard != 0 || !c->d_tables.e || !c->d_wtables.e) return FTS_API_EINVAL;  // host-only: no tables
+  o->narrow_id = c->d_tables.e->id, o->wide_id = c->d_wtables.e->id;
+  o->narrow_bytes = c->d_tables.e->bytes, o->wide_bytes = c->d_wtables.e->bytes;
+  o->narrow_refs = DevTableCache::refs(c->d_tables.e), o->wide_refs = DevTableCache::refs(c->d_wtables.e);
+  o->narrow_built = c->d_tables.built, o->wide_built = c->d_wtables.built;
+  return FTS_API_OK;
+}
+
+int fts_table_cache_stats(int device, struct fts_table_cache_stats* o) {
+  if (!o) return FTS_API_EINVAL;
+  const TableCacheStats s = table_cache().stats(device);
+  o->resident_bytes = s.resident_bytes;
+  o->entries = s.entries;
+  o->builds = s.builds, o->hits = s.hits;
   return FTS_API_OK;
 }
 

@@ -38,6 +38,7 @@
 #include "host_pool.hpp"
 #include "pp_parse.hpp"
 #include "request_parse.hpp"
+#include "table_cache.hpp"
 #include "proofs.hpp"
 #include "prover.hpp"
 
@@ -187,6 +188,36 @@ struct Lane {
   }
 };
 
+// Device policy of the table cache: the entry's device is made current before its
+// buffer is allocated or freed (the last context to let go may run anywhere).
+struct DevTableMem {
+  static void* alloc(int device, size_t bytes) {
+    void* p = nullptr;
+    if (hipSetDevice(device) != hipSuccess || hipMalloc(&p, bytes) != hipSuccess) {
+      (void)hipGetLastError();
+      return nullptr;
+    }
+    return p;
+  }
+  static void free(int device, void* p) {
+    (void)hipSetDevice(device);
+    (void)hipFree(p);
+  }
+};
+using DevTableCache = TableCache<DevTableMem>;
+// the process's one table cache [api_ctx.cpp]
+DevTableCache& table_cache();
+
+// a context's reference to one table set
+struct TableRef {
+  DevTableCache::Ref e;
+  bool built = false;  // this context's creation built it (else: found in the cache)
+  template <class T>
+  const T* as() const {
+    return e ? e->as<T>() : nullptr;
+  }
+};
+
 struct ActSlot;
 struct fts_rp_batch {
   int B = 0;
@@ -283,8 +314,10 @@ struct fts_ctx {
   std::vector<fts_ctx*> shards;  // owned (released by the destructor)
   PublicParams pp;
   int n = 0, k = 0;
-  DevBuf d_tables;
-  DevBuf d_wtables;  // wide tables of [H_0 .. H_{n-1}, K, P] (k_rp_fixed_exact)
+  // fixed-base tables: counted references to entries of the device's table cache
+  // (host/table_cache.hpp; private entries with FTS_TABLE_SHARE=0), read-only once built
+  TableRef d_tables;
+  TableRef d_wtables;  // wide tables of [H_0 .. H_{n-1}, K, P] (k_rp_fixed_exact)
   // their window width: 22 bits (12 additions per product, 1.5 GiB per base) when the
   // device has the memory at context creation, else 20 (13, 436 MiB); FTS_WIDE_BITS
   int wbits = 20;

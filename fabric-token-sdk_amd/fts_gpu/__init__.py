@@ -25,6 +25,7 @@ carrying the reference's error string otherwise.  The batch entry points
 aggregates many actions calls; every one of them runs the HIP kernels of
 ``libfts_gpu.so`` — there is no CPU fallback.
 """
+import collections
 import ctypes as C
 
 import numpy as np
@@ -97,6 +98,20 @@ def decode_metadata(raw):
             b.raw if has.value & 2 else None)
 
 
+TableInfo = collections.namedtuple("TableInfo", [f for f, _ in L.TableInfo._fields_])
+TableCacheStats = collections.namedtuple("TableCacheStats", [f for f, _ in L.TableCacheStats._fields_])
+
+
+def table_cache_stats(device=0):
+    """fts_table_cache_stats: the shared fixed-base tables of one device ->
+    :class:`TableCacheStats` (resident_bytes and entries of the live shared entries;
+    builds and hits since the process started).  Contexts created with
+    FTS_TABLE_SHARE=0 own private tables, which are not counted here."""
+    o = L.TableCacheStats()
+    L.check("fts_table_cache_stats", L.lib.fts_table_cache_stats(int(device), C.byref(o)))
+    return TableCacheStats(*(getattr(o, f) for f in TableCacheStats._fields))
+
+
 def _ptr_array(blobs):
     bufs = [C.create_string_buffer(b, len(b)) if b else None for b in blobs]
     ptrs = (C.c_void_p * len(blobs))(*[C.cast(b, C.c_void_p) if b is not None else None for b in bufs])
@@ -162,6 +177,15 @@ class PublicParams:
         out = (C.c_int64 * 4)()
         L.check("fts_debug_pass_stats", L.lib.fts_debug_pass_stats(self._ctx, out))
         return tuple(out)
+
+    def table_info(self, shard=0):
+        """fts_ctx_table_info: the table-cache entries this context (its shard `shard`
+        on a multi-device context) reads -> :class:`TableInfo`.  Equal ids on one
+        device are the same device memory; ``*_refs`` contexts hold the entry now;
+        ``*_built`` is 1 when this context's creation built it, 0 when it was found"""
+        o = L.TableInfo()
+        L.check("fts_ctx_table_info", L.lib.fts_ctx_table_info(self._ctx, int(shard), C.byref(o)))
+        return TableInfo(*(getattr(o, f) for f in TableInfo._fields))
 
     def reserve(self, max_pass_proofs=0):
         """pre-allocate every device lane for passes of up to max_pass_proofs

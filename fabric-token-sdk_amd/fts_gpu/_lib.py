@@ -71,6 +71,7 @@ EXPORTED = [
     "fts_idemix_identity_last_timings", "fts_idemix_identity_last_stats", "fts_idemix_pairing_debug", "fts_ctx_create_opts", "fts_debug_hold",
     "fts_debug_dispatch_stats", "fts_debug_pass_stats", "fts_debug_stage_actions",
     "fts_idemix_audit_match_batch", "fts_idemix_audit_last_timings",
+    "fts_ctx_table_info", "fts_table_cache_stats",
 ]
 
 
@@ -83,6 +84,17 @@ class PPInfo(C.Structure):
 class CtxOpts(C.Structure):
     _fields_ = [("bit_length", C.c_uint32), ("wide_bits", C.c_int32), ("table_budget", C.c_uint64),
                 ("lanes", C.c_int32), ("reserved", C.c_int32)]
+
+
+class TableInfo(C.Structure):
+    _fields_ = [("narrow_id", C.c_uint64), ("wide_id", C.c_uint64), ("narrow_bytes", C.c_uint64),
+                ("wide_bytes", C.c_uint64), ("narrow_refs", C.c_uint32), ("wide_refs", C.c_uint32),
+                ("narrow_built", C.c_uint32), ("wide_built", C.c_uint32)]
+
+
+class TableCacheStats(C.Structure):
+    _fields_ = [("resident_bytes", C.c_uint64), ("entries", C.c_uint32), ("builds", C.c_uint64),
+                ("hits", C.c_uint64)]
 
 
 class TransferItem(C.Structure):
@@ -129,6 +141,8 @@ def _load():
         "fts_ctx_create_bits": ([U8P, S, C.c_uint32, C.c_int, C.POINTER(P)], C.c_int),
         "fts_ctx_destroy": ([P], None),
         "fts_ctx_info": ([P, C.POINTER(PPInfo)], C.c_int),
+        "fts_ctx_table_info": ([P, C.c_int, C.POINTER(TableInfo)], C.c_int),
+        "fts_table_cache_stats": ([C.c_int, C.POINTER(TableCacheStats)], C.c_int),
         "fts_ctx_create_opts": ([U8P, S, C.c_int, C.POINTER(CtxOpts), C.POINTER(P)], C.c_int),
         "fts_debug_hold": ([P, C.c_int], C.c_int),
         "fts_debug_dispatch_stats": ([P, C.POINTER(C.c_int64)], C.c_int),

@@ -160,7 +160,7 @@ int fts_ctx_create_bits(const uint8_t* pp, size_t pp_len, uint32_t bit_length, i
 int fts_ctx_create_opts(const uint8_t* pp, size_t pp_len, int device, const fts_ctx_opts* opts, fts_ctx** out);
 /* Multi-device context (SURVEY §8b device_mask; the reference verifies every action
  * independently, core/common/validator.go:215-224): one child context per device (its
- * own tables, lanes, streams).  Every batch entry point below splits the caller's batch
+ * own lanes and streams; children on one device share its tables, see below).  Every batch entry point below splits the caller's batch
  * into contiguous shards balanced by cost (fts_shard_plan: range proofs per action),
  * runs the shards on their devices concurrently and returns the verdicts in the
  * caller's order; fts_msm_g1 sums the devices' partial MSM points on the host.
@@ -178,6 +178,46 @@ int fts_ctx_devices(const fts_ctx* ctx, int32_t* devices, int cap);
 int fts_shard_plan(size_t n, const double* weights, int nshards, size_t* bounds);
 void fts_ctx_destroy(fts_ctx* ctx);
 int fts_ctx_info(const fts_ctx* ctx, fts_pp_info* out);
+
+/* ---- shared fixed-base tables ----
+ * The tables are a function of the generator bytes alone, so the contexts of one
+ * process that have the same bases on the same device read ONE device buffer: a
+ * process-wide, per-device, reference-counted cache hands it out.  Two kinds of entry:
+ *   narrow  the 16-bit tables of all 2n+6 bases; key = (device, SHA-256 of the bases)
+ *   wide    the 20/22-bit tables of [H_0..H_{n-1}, K, P]; key = (device, width,
+ *           SHA-256 of those n+2 bases) -- the Pedersen generators are not part of it,
+ *           so public parameters that differ only in them share the wide set
+ * Different bit lengths share nothing (K and the layout depend on n).  Contexts created
+ * concurrently with the same key build it once; the others wait.  Each context holds a
+ * counted reference; the last one destroyed frees the buffer, and the cache keeps
+ * nothing alive by itself.  A built table is never written again.
+ * Width: with no explicit width (fts_ctx_opts.wide_bits, FTS_WIDE_BITS) and no
+ * table_budget, a context takes 22-bit tables without looking at the free HBM when a
+ * live context on the device already has (or is building) its wide set at 22 bits.
+ * fts_pp_info.table_bytes stays the size of the tables the context READS (summed over
+ * the shards of a multi-device context), shared or not; table_budget compares against
+ * the same figure.
+ * FTS_TABLE_SHARE=0 (read at context creation): the context builds private tables. */
+typedef struct fts_table_info {
+  uint64_t narrow_id, wide_id;       /* opaque; equal ids on one device = the same device memory */
+  uint64_t narrow_bytes, wide_bytes;
+  uint32_t narrow_refs, wide_refs;   /* contexts holding the entry now */
+  uint32_t narrow_built, wide_built; /* 1: this context's creation built it; 0: found in the cache */
+} fts_table_info;
+/* shard: index into the context's devices (0 for a single-device context).  A private
+ * context (FTS_TABLE_SHARE=0) reports refs 1, built 1 and ids of its own.
+ * FTS_API_EINVAL for a host-only context or a shard out of range. */
+int fts_ctx_table_info(const fts_ctx* ctx, int shard, fts_table_info* out);
+
+/* The cache's books for one device.  Private contexts' tables are not in them.
+ * (The struct shares its name with the call, like stat: write `struct
+ * fts_table_cache_stats`.) */
+struct fts_table_cache_stats {
+  uint64_t resident_bytes;           /* bytes of all live entries on the device */
+  uint32_t entries;
+  uint64_t builds, hits;             /* since process start */
+};
+int fts_table_cache_stats(int device, struct fts_table_cache_stats* out);
 
 /* ---- verification (host buffers in, verdicts out) ---- */
 /* n standalone range proofs: rp_der[i] = RangeProof.Serialize() (bulletproof.go:93-95),
