@@ -350,9 +350,10 @@ int fts_rp_prove_batch_gpu(fts_ctx* c, size_t N, const uint64_t* values, const u
 // range proofs of every output (rp_prove_device), byte-identical to
 // fts_transfer_prove / fts_issue_prove for the same seeds
 // ---------------------------------------------------------------------------
-static int actions_prove_device(fts_ctx* c, size_t A, const fts_action_witness* w, int issue, uint64_t seed,
-                                uint8_t* out, size_t out_cap, size_t* offsets, size_t* lens) {
-  if (!c || !w || !out || !offsets || !lens || A > (size_t)(1u << 22)) return FTS_API_EINVAL;
+int actions_prove_core(fts_ctx* c, size_t A, const fts_action_witness* w, int issue, const RngSource& src,
+                       std::vector<std::string>& der) {
+  if (!c || !w || A > (size_t)(1u << 22)) return FTS_API_EINVAL;
+  der.assign(A, std::string());
   if (A == 0) return FTS_API_OK;
   if (c->device < 0) return FTS_API_EDEVICE;
   const int n = c->n, nr = pv_nrnd(n), kind = issue ? 1 : 0;
@@ -363,7 +364,6 @@ static int actions_prove_device(fts_ctx* c, size_t A, const fts_action_witness* 
         (x.type_len && !x.type) || nin > 4096 || x.n_out > 4096)
       return FTS_API_EINVAL;
   }
-  RngSource src(seed);
   if (!src.ok) return FTS_API_EDEVICE;
   HIP_OK(hipSetDevice(c->device));
   LaneGuard lg(c);
@@ -465,7 +465,6 @@ static int actions_prove_device(fts_ctx* c, size_t A, const fts_action_witness* 
     if (rc) return rc;
   }
   // host: DER (transfer.go:140-149 / issue/prover.go:100-111)
-  std::vector<std::string> der(A);
   bool bad = false;
   parallel_for(A, 64, [&](size_t a) {
     const SpAction& ac = act[a];
@@ -492,6 +491,18 @@ static int actions_prove_device(fts_ctx* c, size_t A, const fts_action_witness* 
     }
   });
   if (bad) return FTS_API_EDEVICE;
+  return FTS_API_OK;
+}
+
+static int actions_prove_device(fts_ctx* c, size_t A, const fts_action_witness* w, int issue, uint64_t seed,
+                                uint8_t* out, size_t out_cap, size_t* offsets, size_t* lens) {
+  if (!c || !w || !out || !offsets || !lens || A > (size_t)(1u << 22)) return FTS_API_EINVAL;
+  if (A == 0) return FTS_API_OK;
+  if (c->device < 0) return FTS_API_EDEVICE;
+  RngSource src(seed);
+  std::vector<std::string> der;
+  int rc = actions_prove_core(c, A, w, issue, src, der);
+  if (rc) return rc;
   size_t off = 0;
   for (size_t a = 0; a < A; a++) {
     offsets[a] = off;

@@ -107,6 +107,14 @@ void launch_sigma_prove(const SpDev& d, hipStream_t s);
 // ---- audit_kernels.hip
 void launch_open_check(int n, const uint8_t* raw, const uint32_t* sc, const uint32_t* tables, int nb,
                        int32_t* status, hipStream_t s);
+// tokens per lane of k_token_commit (they share one inversion).  1: at 65,536 tokens a lane
+// per token is one wave per SIMD, and every further token per lane only takes waves
+// off the chip (0.40 ms against 0.70 / 1.32 / 2.49 / 4.85 ms for 2 / 4 / 8 / 16; at 2^20 tokens
+// 2 and 4 gain 4 %); the launcher takes 2 / 4 / 8 / 16 for that A/B
+constexpr int TOKEN_COMMIT_PER_LANE = 1;
+// sc: [n][24] staged scalars; zs, pre: [n][8] scratch; out: [n][64] (16-byte aligned)
+void launch_token_commit(int n, int per_lane, const uint32_t* sc, const uint32_t* tables, int nb, uint32_t* zs,
+                         uint32_t* pre, uint8_t* out, hipStream_t s);
 
 // ---- idemix_kernels.hip (nym signatures; the FP256BN fixed-base tables also serve the identity proofs)
 void fbn_build_tables(const uint32_t* plain, int nb, uint32_t* mont, int32_t* ok, uint32_t* tables, hipStream_t s);

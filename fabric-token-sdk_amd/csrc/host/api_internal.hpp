@@ -1,7 +1,7 @@
 // Shared by the units of the C-ABI (include/fts_gpu.h): api_ctx.cpp (contexts,
 // multi-device layer), api_rp.cpp (range-proof passes and their dispatcher),
-// api_msm.cpp, api_actions.cpp (transfers / issues / requests), api_prove.cpp and
-// api_audit.cpp.
+// api_msm.cpp, api_actions.cpp (transfers / issues / requests), api_prove.cpp,
+// api_generate.cpp and api_audit.cpp.
 //
 // Host side of the drop-in boundary: context creation from the public
 // parameters (setup.go:319-372), DER decoding of proofs into device records,
@@ -496,6 +496,14 @@ int lane_reserve(fts_ctx* c, Lane& L, int B, bool inputs);
 int rp_dispatch(fts_ctx* c, RpReq& me);
 // the context's host prover tables, built on first use [api_prove.cpp]
 const ProverTables& prover_tables(const fts_ctx* cc);
+// A whole transfer (issue = 0) / issue proofs on one device context, action a drawing
+// from src.at(a): der[a] <- the proof of fts_transfer_prove / fts_issue_prove [api_prove.cpp]
+int actions_prove_core(fts_ctx* c, size_t A, const fts_action_witness* w, int issue, const RngSource& src,
+                       std::vector<std::string>& der);
+// n token commitments on one device context: item(i, type, type_len, value, bf32) names
+// token i; com64_out[i] <- its 64 bytes [api_generate.cpp]
+using CommitItem = std::function<void(size_t, const uint8_t*&, size_t&, uint64_t&, const uint8_t*&)>;
+int token_commit_device(fts_ctx* c, size_t n, const CommitItem& item, uint8_t* com64_out);
 
 // run f(j, lo, hi) for every non-empty shard j concurrently; first error wins
 template <class F>

@@ -98,6 +98,12 @@ def decode_metadata(raw):
             b.raw if has.value & 2 else None)
 
 
+def token_commit_batch_width():
+    """tokens per wave of the device commit kernel (fts_token_commit_batch_width): 64 lanes
+    times the tokens a lane normalises with one inversion"""
+    return int(L.lib.fts_token_commit_batch_width())
+
+
 TableInfo = collections.namedtuple("TableInfo", [f for f, _ in L.TableInfo._fields_])
 TableCacheStats = collections.namedtuple("TableCacheStats", [f for f, _ in L.TableCacheStats._fields_])
 
@@ -316,6 +322,55 @@ class PublicParams:
         out = C.create_string_buffer(64)
         L.check("fts_token_commit", L.lib.fts_token_commit(self._ctx, ttype, len(ttype), value, bf32, out))
         return out.raw
+
+    def token_commit_batch_gpu(self, items):
+        """fts_token_commit_batch_gpu: items = [(type, value, bf32)] -> the 64-byte
+        commitments, each the bytes of token_commit on the same arguments"""
+        n = len(items)
+        arr = (L.CommitItem * max(1, n))()
+        keep = []
+        for i, (t, v, bf) in enumerate(items):
+            bt, bb = C.create_string_buffer(t or b"\0", max(1, len(t))), C.create_string_buffer(bf, 32)
+            keep += [bt, bb]
+            arr[i] = L.CommitItem(C.cast(bt, C.c_void_p), len(t), v, C.cast(bb, C.c_void_p))
+        out = C.create_string_buffer(64 * max(1, n))
+        L.check("fts_token_commit_batch_gpu", L.lib.fts_token_commit_batch_gpu(self._ctx, n, arr, out))
+        raw = out.raw  # one copy: .raw copies the whole buffer on every access
+        return [raw[64 * i:64 * i + 64] for i in range(n)]
+
+    def _generate(self, fn, batch, seed, single):
+        gb = batch if isinstance(batch, GenBatch) else GenBatch(batch, self.rounds)
+        r = gb.result()
+        if single:
+            L.check(fn, getattr(L.lib, fn)(self._ctx, gb.items, seed, C.byref(r.c)))
+        else:
+            L.check(fn, getattr(L.lib, fn)(self._ctx, gb.n, gb.items, seed, C.byref(r.c)))
+        return r.unpack(gb)
+
+    def generate_transfer(self, ttype, inputs, outputs, seed):
+        """Sender.GenerateZKTransfer on the host (fts_transfer_generate): inputs =
+        [(tx_id, index, owner, com64, value, bf32)], outputs = [(value, owner)] (owner
+        b"": a redeem) -> (action bytes, [metadata bytes], [com64], [bf32]) per output"""
+        return self._generate("fts_transfer_generate", [(ttype, inputs, outputs, b"")], seed, True)[0]
+
+    def generate_issue(self, ttype, issuer, outputs, seed):
+        """Issuer.GenerateZKIssue on the host (fts_issue_generate): outputs = [(value,
+        owner)] -> (action bytes, [metadata bytes], [com64], [bf32])"""
+        return self._generate("fts_issue_generate", [(ttype, [], outputs, issuer)], seed, True)[0]
+
+    def generate_transfers_gpu(self, transfers, seed):
+        """fts_transfer_generate_batch_gpu: transfers = [(type, inputs, outputs)] (or a
+        GenBatch) -> one generate_transfer result per action, action i that of seed + i"""
+        if not isinstance(transfers, GenBatch):
+            transfers = GenBatch([(t, i, o, b"") for t, i, o in transfers], self.rounds)
+        return self._generate("fts_transfer_generate_batch_gpu", transfers, seed, False)
+
+    def generate_issues_gpu(self, issues, seed):
+        """fts_issue_generate_batch_gpu: issues = [(type, issuer, outputs)] (or a GenBatch)
+        -> one generate_issue result per action, action i that of seed + i"""
+        if not isinstance(issues, GenBatch):
+            issues = GenBatch([(t, [], o, iss) for t, iss, o in issues], self.rounds)
+        return self._generate("fts_issue_generate_batch_gpu", issues, seed, False)
 
     def prove_range(self, value, bf32, seed):
         buf = C.create_string_buffer(1 << 14)
@@ -632,6 +687,79 @@ class WitnessBatch:
         self.cap = 4096 + sum(1024 + 200 * len(a[1]) + len(a[3]) * (1500 + 150 * rounds) for a in actions)
         self._cols = np.ascontiguousarray(cols)
         self.items = self._cols.ctypes.data_as(C.POINTER(L.ActionWitness))
+
+
+class GenBatch:
+    """fts_gen_action[] (kept alive with the batch): actions = [(type, inputs, outputs,
+    issuer)], inputs = [(tx_id, index, owner, com64, value, bf32)], outputs = [(value,
+    owner)]; reusable across generate calls"""
+
+    def __init__(self, actions, rounds=6):
+        n = self.n = len(actions)
+        self._keep = []
+
+        def buf(b):
+            if not b:
+                return None
+            a = C.create_string_buffer(bytes(b), len(b))
+            self._keep.append(a)
+            return C.cast(a, C.c_void_p)
+
+        self.items = (L.GenAction * max(1, n))()
+        self.n_out = []
+        self.acap, self.mcap = 4096, 4096
+        for k, (t, ins, outs, issuer) in enumerate(actions):
+            ia = (L.GenInput * max(1, len(ins)))()
+            for q, (tx, idx, owner, com, v, bf) in enumerate(ins):
+                ia[q] = L.GenInput(buf(tx), len(tx), idx, buf(owner), len(owner), buf(com), v, buf(bf))
+                self.acap += 256 + len(tx) + len(owner)
+            oa = (L.GenOutput * max(1, len(outs)))()
+            for q, (v, owner) in enumerate(outs):
+                oa[q] = L.GenOutput(v, buf(owner), len(owner))
+                self.acap += 256 + len(owner) + 1500 + 150 * rounds
+                self.mcap += 256 + len(t) + len(issuer)
+            self.acap += 1024 + 200 * len(ins) + len(issuer)
+            self._keep += [ia, oa]
+            self.items[k] = L.GenAction(buf(t), len(t), C.cast(ia, C.c_void_p), len(ins), C.cast(oa, C.c_void_p),
+                                        len(outs), buf(issuer), len(issuer))
+            self.n_out.append(len(outs))
+        self.total_out = sum(self.n_out)
+
+    def result(self):
+        return GenResult(self)
+
+
+class GenResult:
+    """caller buffers of one generate call (fts_gen_result)"""
+
+    def __init__(self, gb):
+        T = max(1, gb.total_out)
+        self.actions = np.empty(gb.acap, dtype=np.uint8)
+        self.meta = np.empty(gb.mcap, dtype=np.uint8)
+        self.aoff, self.alen = (C.c_size_t * max(1, gb.n))(), (C.c_size_t * max(1, gb.n))()
+        self.moff, self.mlen = (C.c_size_t * T)(), (C.c_size_t * T)()
+        self.com, self.bf = np.empty(64 * T, dtype=np.uint8), np.empty(32 * T, dtype=np.uint8)
+        ptr = lambda a: C.cast(a, C.c_void_p)  # noqa: E731
+        self.c = L.GenResult(self.actions.ctypes.data, gb.acap, ptr(self.aoff), ptr(self.alen), self.meta.ctypes.data,
+                             gb.mcap, ptr(self.moff), ptr(self.mlen), self.com.ctypes.data, self.bf.ctypes.data)
+
+    def unpack(self, gb):
+        """[(action bytes, [metadata bytes], [com64], [bf32])] per action"""
+        if not gb.n:
+            return []
+        act = self.actions[:self.aoff[gb.n - 1] + self.alen[gb.n - 1]].tobytes()
+        T = gb.total_out
+        meta = self.meta[:self.moff[T - 1] + self.mlen[T - 1]].tobytes()
+        com, bf = self.com.tobytes(), self.bf.tobytes()
+        out, t = [], 0
+        for i in range(gb.n):
+            m = gb.n_out[i]
+            out.append((act[self.aoff[i]:self.aoff[i] + self.alen[i]],
+                        [meta[self.moff[t + j]:self.moff[t + j] + self.mlen[t + j]] for j in range(m)],
+                        [com[64 * (t + j):64 * (t + j) + 64] for j in range(m)],
+                        [bf[32 * (t + j):32 * (t + j) + 32] for j in range(m)]))
+            t += m
+        return out
 
 
 class Auditor:

@@ -72,6 +72,8 @@ EXPORTED = [
     "fts_debug_dispatch_stats", "fts_debug_pass_stats", "fts_debug_stage_actions",
     "fts_idemix_audit_match_batch", "fts_idemix_audit_last_timings",
     "fts_ctx_table_info", "fts_table_cache_stats",
+    "fts_token_commit_batch_gpu", "fts_token_commit_batch_width", "fts_transfer_generate", "fts_issue_generate",
+    "fts_transfer_generate_batch_gpu", "fts_issue_generate_batch_gpu",
 ]
 
 
@@ -129,6 +131,30 @@ class AuditItem(C.Structure):
 class ActionWitness(C.Structure):
     _fields_ = [("type", C.c_void_p), ("type_len", C.c_size_t), ("n_in", C.c_size_t), ("in_values", C.c_void_p),
                 ("in_bfs", C.c_void_p), ("n_out", C.c_size_t), ("out_values", C.c_void_p), ("out_bfs", C.c_void_p)]
+
+
+class CommitItem(C.Structure):
+    _fields_ = [("type", C.c_void_p), ("type_len", C.c_size_t), ("value", C.c_uint64), ("bf32", C.c_void_p)]
+
+
+class GenInput(C.Structure):
+    _fields_ = [("tx_id", C.c_void_p), ("tx_id_len", C.c_size_t), ("index", C.c_uint64), ("owner", C.c_void_p),
+                ("owner_len", C.c_size_t), ("com64", C.c_void_p), ("value", C.c_uint64), ("bf32", C.c_void_p)]
+
+
+class GenOutput(C.Structure):
+    _fields_ = [("value", C.c_uint64), ("owner", C.c_void_p), ("owner_len", C.c_size_t)]
+
+
+class GenAction(C.Structure):
+    _fields_ = [("type", C.c_void_p), ("type_len", C.c_size_t), ("inputs", C.c_void_p), ("n_in", C.c_size_t),
+                ("outputs", C.c_void_p), ("n_out", C.c_size_t), ("issuer", C.c_void_p), ("issuer_len", C.c_size_t)]
+
+
+class GenResult(C.Structure):
+    _fields_ = [("actions", C.c_void_p), ("actions_cap", C.c_size_t), ("action_off", C.c_void_p),
+                ("action_len", C.c_void_p), ("meta", C.c_void_p), ("meta_cap", C.c_size_t), ("meta_off", C.c_void_p),
+                ("meta_len", C.c_void_p), ("com64", C.c_void_p), ("bf32", C.c_void_p)]
 
 
 def _load():
@@ -213,6 +239,12 @@ def _load():
         "fts_idemix_pairing_debug": ([P, C.c_int, U8P, C.c_int, C.POINTER(C.c_uint32)], C.c_int),
         "fts_idemix_audit_match_batch": ([P, S, C.POINTER(AuditItem), I32P], C.c_int),
         "fts_idemix_audit_last_timings": ([P, C.POINTER(C.c_float)], C.c_int),
+        "fts_token_commit_batch_gpu": ([P, S, C.POINTER(CommitItem), P], C.c_int),
+        "fts_token_commit_batch_width": ([], C.c_int),
+        "fts_transfer_generate": ([P, C.POINTER(GenAction), C.c_uint64, C.POINTER(GenResult)], C.c_int),
+        "fts_issue_generate": ([P, C.POINTER(GenAction), C.c_uint64, C.POINTER(GenResult)], C.c_int),
+        "fts_transfer_generate_batch_gpu": ([P, S, C.POINTER(GenAction), C.c_uint64, C.POINTER(GenResult)], C.c_int),
+        "fts_issue_generate_batch_gpu": ([P, S, C.POINTER(GenAction), C.c_uint64, C.POINTER(GenResult)], C.c_int),
     }
     for name, (args, res) in sig.items():
         try:

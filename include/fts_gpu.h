@@ -435,6 +435,96 @@ int fts_transfer_prove(const fts_ctx* ctx, const uint8_t* type, size_t type_len,
 int fts_issue_prove(const fts_ctx* ctx, const uint8_t* type, size_t type_len, size_t n_tok, const uint64_t* values,
                     const uint8_t* bfs, uint64_t seed, uint8_t* out_der, size_t out_cap, size_t* out_len);
 
+/* Token commitments for a batch on the device (audit_kernels.hip k_token_commit): replaces the
+ * per-token commit() of token.GetTokensWithWitness (crypto/token/token.go:109-133, commit :208-217).
+ *   com64_out[i] <- G1.Bytes() of HashToZr(type_i)*ped0 + value_i*ped1 + bf_i*ped2
+ * byte-identical to fts_token_commit on the same arguments (bf32: 32 B BE, used mod r; the
+ * identity comes out as 64 zero bytes).  Three fixed-base products per token into one
+ * accumulator, then the exact affine point.  Needs a device context (FTS_API_EDEVICE
+ * otherwise); a multi-device context runs it on its first device, as the provers do. */
+typedef struct {
+  const uint8_t* type;
+  size_t type_len;
+  uint64_t value;
+  const uint8_t* bf32;
+} fts_commit_item;
+int fts_token_commit_batch_gpu(fts_ctx* ctx, size_t n, const fts_commit_item* items, uint8_t* com64_out);
+/* tokens per wave of that kernel: 64 lanes x the tokens a lane commits and normalises with
+ * one inversion (1 by default: DESIGN.md section 5.3) */
+int fts_token_commit_batch_width(void);
+
+/* ---- whole transfer / issue actions (prover side of the TokenRequest) ----
+ * Replaces Sender.GenerateZKTransfer (crypto/transfer/sender.go:54-107) and
+ * Issuer.GenerateZKIssue (crypto/issue/issuer.go:39-84): draw the output blinding factors,
+ * commit the outputs (token.GetTokensWithWitness, token.go:109-133), prove
+ * (transfer.go:69-150 / issue/prover.go:46-112), build the action (NewTransfer
+ * transfer/action.go:127-153 / NewAction issue/action.go:62-77) and serialize it
+ * (Action.Serialize transfer/action.go:290-323 / issue/action.go:192-229: fields in number
+ * order, proto3 empty values omitted, no metadata map), and serialize the token.Metadata of
+ * every output (token.go:161-180: TypedToken{2, TokenMetadata{type, value, blinding_factor,
+ * issuer}}; issues carry the issuer, transfers the empty Identity written for a nil issuer).
+ * The checks are those of the reference and of the provers: a transfer whose sums differ,
+ * or a value above the range, yields an action whose proof fails; input commitments are not
+ * checked against their openings.
+ * Randomness: action i's prover draws are those of fts_transfer_prove / fts_issue_prove at
+ * seed + i; its output blinding factors come from stream 2^63 + i of the same source
+ * (secure: that ChaCha20 nonce under the call's key; seeded: xoshiro256**(seed + 2^63 + i)),
+ * drawn uniformly below r in output order.  So commitment = fts_token_commit(type, v_j, bf_j)
+ * and proof = fts_transfer_prove(type, in..., out_values, those bfs, seed + i). */
+typedef struct {
+  const uint8_t* tx_id;  /* token id (token.ID{TxId, Index}) */
+  size_t tx_id_len;
+  uint64_t index;
+  const uint8_t* owner;
+  size_t owner_len;
+  const uint8_t* com64;  /* token.Data, 64 B X||Y BE */
+  uint64_t value;        /* its opening */
+  const uint8_t* bf32;
+} fts_gen_input;
+typedef struct {
+  uint64_t value;
+  const uint8_t* owner;  /* owner_len == 0: a redeem (no owner field is written) */
+  size_t owner_len;
+} fts_gen_output;
+typedef struct {
+  const uint8_t* type;
+  size_t type_len;
+  const fts_gen_input* inputs;  /* transfers; ignored by issues */
+  size_t n_in;
+  const fts_gen_output* outputs;
+  size_t n_out;
+  const uint8_t* issuer;  /* issues; ignored by transfers */
+  size_t issuer_len;
+} fts_gen_action;
+/* Caller buffers.  Outputs are numbered across the call in action order (T = sum of n_out):
+ * action i is actions[action_off[i] .. + action_len[i]), output t's metadata
+ * meta[meta_off[t] .. + meta_len[t]), its commitment com64[64 t] and blinding factor
+ * bf32[32 t] (com64 / bf32: T x 64 / T x 32 bytes).  Every length is computed before
+ * anything is written: when actions_cap or meta_cap is too small the call returns
+ * FTS_API_ESIZE with the offset and length arrays filled and the buffers untouched. */
+typedef struct {
+  uint8_t* actions;
+  size_t actions_cap;
+  size_t* action_off;
+  size_t* action_len;
+  uint8_t* meta;
+  size_t meta_cap;
+  size_t* meta_off;
+  size_t* meta_len;
+  uint8_t* com64;
+  uint8_t* bf32;
+} fts_gen_result;
+/* one action on the host (works on a host-only context, like fts_transfer_prove) */
+int fts_transfer_generate(const fts_ctx* ctx, const fts_gen_action* action, uint64_t seed, fts_gen_result* out);
+int fts_issue_generate(const fts_ctx* ctx, const fts_gen_action* action, uint64_t seed, fts_gen_result* out);
+/* n actions on the device: commitments by k_token_commit, proofs by the passes of
+ * fts_transfer_prove_batch_gpu / fts_issue_prove_batch_gpu, serialization on the host pool.
+ * Action i equals the host call at seed + i.  Needs a device context (FTS_API_EDEVICE). */
+int fts_transfer_generate_batch_gpu(fts_ctx* ctx, size_t n, const fts_gen_action* actions, uint64_t seed,
+                                    fts_gen_result* out);
+int fts_issue_generate_batch_gpu(fts_ctx* ctx, size_t n, const fts_gen_action* actions, uint64_t seed,
+                                 fts_gen_result* out);
+
 /* ---- ECDSA P-256 owner signatures (x509 identities) ----
  * Replaces, per item, ecdsa.Verifier.Verify(message, sigma)
  * (validator/ecdsa/ecdsa.go:82-113; identical logic in

@@ -1,6 +1,6 @@
 #!/bin/bash
 # The measurement recipe behind profiles/ (run on the gpurun box from the repo root):
-#   bash tools/gpu_session.sh STEP...     STEP in: smoke tests rp prof pmc tamper identity identity_pmc msm_pmc extra
+#   bash tools/gpu_session.sh STEP...     STEP in: smoke tests rp prof pmc tamper identity identity_pmc msm_pmc extra generate
 # smoke     __graft_entry__.smoke()
 # tests     pytest -m gpu (full suite)
 # rp        C2 headline, driver shape (20 steps) and steady state (512 steps)
@@ -13,6 +13,7 @@
 # identity_pmc  FETCH_SIZE / WRITE_SIZE per identity kernel (BN254) -> identity_traffic_$TAG.json
 # msm_pmc   FETCH_SIZE / WRITE_SIZE per MSM kernel of C3 at 2^22 points -> msm22_traffic_$TAG.json
 # extra     C3-C5 and SURVEY 8f workloads
+# generate  tools/generate_bench.py: commit kernel A/B, action generation vs the caller-side baseline
 # Every GPU step has its own time limit; the first failure ends the script.
 # Output: gpurun_out/$TAG (TAG default r05).
 set -o pipefail
@@ -80,6 +81,9 @@ for s in "$@"; do case $s in
          step bench_ecdsa 300 python3 -u bench.py --full --workload ecdsa --steps 64 --warmup 4
          step bench_idemix 300 python3 -u bench.py --full --workload idemix --steps 32 --warmup 4
          for w in transfer mixed request msm22 audit prove ecdsa idemix; do json bench_$w; done ;;
+  generate) # commit kernel A/B and generation against the caller-side baseline (PARENT_LIB: a build of the parent commit)
+         step generate 900 python3 -u tools/generate_bench.py ${PARENT_LIB:+--parent-lib $PARENT_LIB} --out $OUT/generate.json
+         grep -v '^wrote' $OUT/generate.log | cut -c1-300 ;;
   *) echo "unknown step $s"; exit 2 ;;
 esac; done
 echo "== done $(date +%T)"
