@@ -470,6 +470,7 @@ const char* fts_status_str(int32_t s) {
     case FTS_E_AUDIT_NO_RHNYM: return "error while verifying the nym rh: no RhNym provided";
     case FTS_E_AUDIT_RH_POINT: return "error while verifying the nym rh: invalid RhNym point";
     case FTS_E_AUDIT_RH_MISMATCH: return "error while verifying the nym rh: rh nym does not match";
+    case FTS_E_SIGN_BADKEY: return "signing key out of range";
     default: return "unknown status";
   }
 }

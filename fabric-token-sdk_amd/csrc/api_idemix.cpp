@@ -23,6 +23,8 @@
 #include "host/hip_owned.hpp"
 #include "host/host_pool.hpp"
 #include "host/idemix_parse.hpp"
+#include "host/prover.hpp"  // Rng, RngSource: the signer's nonces
+#include "host/sign_encode.hpp"
 
 using namespace fts;
 using namespace idv;
@@ -43,6 +45,7 @@ struct NymSlot {
   PinBuf h_buf;  // pinned staging of everything above but vtab
   Event ev[2];
   float ms = 0.f;
+  float sign_ms = 0.f;
 };
 
 constexpr int IDV_NSLOT = 8;  // calls in flight per handle (each slot: its own stream and buffers, grown on first use;
@@ -90,6 +93,13 @@ bool base_words(bool bn, const uint8_t (*raw)[64], int nb, uint32_t* bases) {
   return true;
 }
 
+// Fr (Montgomery) -> canonical LE limbs
+void fr_canon(const host::Fr& a, uint32_t out[8]) {
+  uint64_t c[4];
+  host::from_mont(a, c);
+  for (int i = 0; i < 4; i++) out[2 * i] = (uint32_t)c[i], out[2 * i + 1] = (uint32_t)(c[i] >> 32);
+}
+
 }  // namespace
 
 struct fts_idemix_ipk {
@@ -100,6 +110,7 @@ struct fts_idemix_ipk {
   uint8_t hash[32];
   SlotRing<NymSlot, NYM_NSLOT> ring;
   float last_ms = 0.f;     // under ring.mu
+  float last_sign_ms = 0.f;  // under ring.mu
   size_t tile = NYM_TILE;  // items per launch (FTS_NYM_TILE overrides, for tests)
   ~fts_idemix_ipk() {
     if (device >= 0) (void)hipSetDevice(device);
@@ -294,6 +305,140 @@ int fts_nym_last_timings(fts_idemix_ipk* K, float* ms) {
   if (!K || !ms) return FTS_API_EINVAL;
   std::lock_guard<std::mutex> l(K->ring.mu);
   *ms = K->last_ms;
+  return FTS_API_OK;
+}
+
+int fts_nym_sign_batch(fts_idemix_ipk* K, size_t n, const fts_nym_sign_item* items, uint64_t seed, uint8_t* sig,
+                       int32_t* status) {
+  if (!K || n > (size_t)(1u << 24) || (n && (!items || !sig || !status))) return FTS_API_EINVAL;
+  if (n == 0) return FTS_API_OK;
+  const bool bn = K->curve == FTS_CURVE_BN254;
+  const uint32_t* const rmod = bn ? u256::kRbn : u256::kRfbn;
+  const size_t pre = bn ? 0 : 166;  // the hashed stream, laid out as for fts_nym_verify_batch
+  size_t mtot_w = 0;
+  for (size_t i = 0; i < n; i++) {
+    if (items[i].msg_len > 0xffffff00u || (items[i].msg_len && !items[i].msg)) return FTS_API_EINVAL;
+    mtot_w += (pre + items[i].msg_len + 3) / 4 + 1;
+  }
+  const host::RngSource src(seed);
+  if (!src.ok) return FTS_API_EDEVICE;
+  auto guard = K->ring.acquire([K](NymSlot& S) { K->last_sign_ms = S.sign_ms; });
+  NymSlot& D = guard.slot();
+  ICHK(hipSetDevice(K->device));
+  // layout: secrets | nym | moff | mlen | status | c, s_sk, s_r (device -> host) | messages
+  const size_t sec_b = n * NSREC * 4, nym_b = n * 64, off_b = n * 8, len_b = n * 4, st_b = n * 4, out_b = n * NSOUT * 4;
+  const size_t o_nym = sec_b, o_off = o_nym + nym_b, o_len = o_off + off_b, o_st = o_len + len_b, o_out = o_st + st_b,
+               o_msg = (o_out + out_b + 255) & ~size_t(255), need = o_msg + mtot_w * 4;
+  if (D.h_buf.cap < need && !D.h_buf.reserve(need + need / 2)) return FTS_API_ENOMEM;
+  if (D.d_buf.cap < need && !D.d_buf.reserve(need + need / 2)) return FTS_API_ENOMEM;
+  uint8_t* h = D.h_buf.as<uint8_t>();
+  uint8_t* d = D.d_buf.as<uint8_t>();
+  SecretWipe wipe(D.stream);
+  wipe.host = h, wipe.bytes = sec_b;
+  uint64_t* hoff = reinterpret_cast<uint64_t*>(h + o_off);
+  {
+    uint64_t o = 0;
+    for (size_t i = 0; i < n; i++) hoff[i] = o, o += (pre + items[i].msg_len + 3) / 4 + 1;
+  }
+  // uniform below r by rejection: Rng::fr() on BN254, the same construction over the
+  // 256-bit r of FP256BN (four words, no mask)
+  auto draw = [&](host::Rng& rng, uint32_t out[8]) {
+    if (bn) return fr_canon(rng.fr(), out);
+    do {
+      for (int k = 0; k < 4; k++) {
+        const uint64_t v = rng.next();
+        out[2 * k] = (uint32_t)v, out[2 * k + 1] = (uint32_t)(v >> 32);
+      }
+    } while (u256::ge(out, u256::kRfbn));
+  };
+  const size_t CH = 2048, nch = (n + CH - 1) / CH;
+  host_parallel_for(nch, [&](size_t c) {
+    for (size_t i = c * CH; i < std::min(n, (c + 1) * CH); i++) {
+      const fts_nym_sign_item& it = items[i];
+      uint32_t* R = reinterpret_cast<uint32_t*>(h) + i * NSREC;
+      memset(R, 0, NSREC * 4);
+      int32_t st = FTS_OK;
+      // secrets below r, decided here; then the key checks of verification (the point
+      // checks run on the device)
+      if (!it.sk32 || !it.rnym32 || !u256::be_limbs(it.sk32, 32, R) || !u256::be_limbs(it.rnym32, 32, R + 8) ||
+          u256::ge(R, rmod) || u256::ge(R + 8, rmod))
+        st = FTS_E_SIGN_BADKEY;
+      uint8_t* nr = h + o_nym + i * 64;
+      const bool key_ok = it.nym && (bn ? it.nym_len == 64 : it.nym_len == 65 && it.nym[0] == 0x04);
+      if (key_ok) memcpy(nr, it.nym + (bn ? 0 : 1), 64);
+      else memset(nr, 0, 64);
+      if (st == FTS_OK && !key_ok) st = FTS_E_NYM_BADKEY;
+      if (st == FTS_OK) {
+        host::Rng rng = src.at(i);
+        uint32_t nonce[8];
+        draw(rng, nonce);
+        draw(rng, R + 16);
+        draw(rng, R + 24);
+        for (int k = 0; k < 8; k++) R[32 + k] = nonce[7 - k];  // big-endian words, as hashed
+      } else {
+        memset(R, 0, NSREC * 4);
+      }
+      reinterpret_cast<int32_t*>(h + o_st)[i] = st;
+      reinterpret_cast<uint32_t*>(h + o_len)[i] = (uint32_t)(pre + it.msg_len);
+      uint8_t* mw = h + o_msg + hoff[i] * 4;
+      const size_t wl = ((pre + it.msg_len + 3) / 4 + 1) * 4;
+      if (!bn) {  // "sign" || 0x04 || t (device) || Nym || ipk.Hash
+        memcpy(mw, "sign", 4);
+        mw[4] = 0x04;
+        memset(mw + 5, 0, 64);
+        if (key_ok) memcpy(mw + 69, it.nym, 65);
+        else memset(mw + 69, 0, 65);
+        memcpy(mw + 134, K->hash, 32);
+      }
+      if (it.msg_len) memcpy(mw + pre, it.msg, it.msg_len);
+      memset(mw + pre + it.msg_len, 0, wl - pre - it.msg_len);
+    }
+  });
+  wipe.dev = d;
+  ICHK(hipMemcpyAsync(d, h, o_out, hipMemcpyHostToDevice, D.stream));
+  ICHK(hipMemcpyAsync(d + o_msg, h + o_msg, mtot_w * 4, hipMemcpyHostToDevice, D.stream));
+  ICHK(hipEventRecord(D.ev[0], D.stream));
+  launch_nym_sign(bn, (int)n, reinterpret_cast<const uint32_t*>(d), d + o_nym,
+                  reinterpret_cast<const uint32_t*>(d + o_msg), reinterpret_cast<const uint64_t*>(d + o_off),
+                  reinterpret_cast<const uint32_t*>(d + o_len), K->d_tables.as<uint32_t>(), K->d_hash.as<uint32_t>(),
+                  reinterpret_cast<int32_t*>(d + o_st), reinterpret_cast<uint32_t*>(d + o_out), D.stream);
+  ICHK(hipGetLastError());
+  ICHK(hipEventRecord(D.ev[1], D.stream));
+  // the nonce words are read back from the staging copy before it is wiped
+  ICHK(hipMemcpyAsync(h + o_st, d + o_st, st_b + out_b, hipMemcpyDeviceToHost, D.stream));
+  ICHK(hipMemsetAsync(d, 0, sec_b, D.stream));
+  wipe.dev = nullptr;  // queued
+  ICHK(hipStreamSynchronize(D.stream));
+  host_parallel_for(nch, [&](size_t c) {
+    for (size_t i = c * CH; i < std::min(n, (c + 1) * CH); i++) {
+      const int32_t st = reinterpret_cast<const int32_t*>(h + o_st)[i];
+      status[i] = st;
+      uint8_t* o = sig + i * FTS_NYM_SIG_LEN;
+      if (st != FTS_OK) {
+        memset(o, 0, FTS_NYM_SIG_LEN);
+        continue;
+      }
+      const uint32_t* O = reinterpret_cast<const uint32_t*>(h + o_out) + i * NSOUT;
+      const uint32_t* R = reinterpret_cast<const uint32_t*>(h) + i * NSREC;
+      uint8_t f[4][32];
+      for (int q = 0; q < 3; q++)
+        for (int k = 0; k < 8; k++)
+          for (int b = 0; b < 4; b++) f[q][4 * k + b] = (uint8_t)(O[8 * q + 7 - k] >> (24 - 8 * b));
+      for (int k = 0; k < 8; k++)
+        for (int b = 0; b < 4; b++) f[3][4 * k + b] = (uint8_t)(R[32 + k] >> (24 - 8 * b));
+      host::nym_sig_proto(f[0], f[1], f[2], f[3], o);
+    }
+  });
+  memset(h, 0, sec_b);
+  wipe.host = nullptr;
+  ICHK(hipEventElapsedTime(&D.sign_ms, D.ev[0], D.ev[1]));
+  return FTS_API_OK;
+}
+
+int fts_nym_sign_last_timings(fts_idemix_ipk* K, float* ms) {
+  if (!K || !ms) return FTS_API_EINVAL;
+  std::lock_guard<std::mutex> l(K->ring.mu);
+  *ms = K->last_sign_ms;
   return FTS_API_OK;
 }
 

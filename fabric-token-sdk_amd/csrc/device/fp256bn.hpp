@@ -26,6 +26,10 @@ struct PM {  // p = 0xFFFFFFFFFFFCF0CD46E5F25EEE71A49F0CDC65FB12980A82D3292DDBAE
 struct RM {  // group order r = 0xFFFFFFFFFFFCF0CD46E5F25EEE71A49E0CDC65FB1299921AF62D536CD10B500D
   static constexpr uint32_t M[8] = {0xd10b500du, 0xf62d536cu, 0x1299921au, 0x0cdc65fbu,
                                     0xee71a49eu, 0x46e5f25eu, 0xfffcf0cdu, 0xffffffffu};
+  // Montgomery constants (nym signing: s = r + c * secret mod r)
+  static constexpr uint32_t INV = 0xc9c6813bu;  // -r^-1 mod 2^32
+  static constexpr uint32_t R2[8] = {0x8f4c4808u, 0xaf948aa3u, 0x26123232u, 0xbd789efdu,
+                                     0xeb526be7u, 0x117fd17cu, 0xfb8f407au, 0x2bfc4998u};
 };
 // 3 in Montgomery form (curve b)
 __device__ constexpr uint32_t CB3[8] = {0xf3866fc7u, 0x8684766cu, 0xc837e077u, 0xd96ace0eu,

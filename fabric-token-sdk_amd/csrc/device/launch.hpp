@@ -123,6 +123,10 @@ size_t fbn_words_per_base();
 void launch_nym_verify(bool bn, int n, const uint32_t* rec, const uint8_t* nym, const uint32_t* msgw,
                        const uint64_t* moff, const uint32_t* mlen, const uint32_t* tables, const uint32_t* ipk_hash,
                        uint32_t* vtab, int32_t* status, int base, int tile, hipStream_t s);
+// k_nym_sign (bn) or k_nym_sign_fbn over all n items: srec idv::NSREC words per item, out idv::NSOUT
+void launch_nym_sign(bool bn, int n, const uint32_t* srec, const uint8_t* nym, const uint32_t* msgw,
+                     const uint64_t* moff, const uint32_t* mlen, const uint32_t* tables, const uint32_t* ipk_hash,
+                     int32_t* status, uint32_t* out, hipStream_t s);
 
 }  // namespace fts
 

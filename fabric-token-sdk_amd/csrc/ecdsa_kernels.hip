@@ -19,6 +19,12 @@
 //                   mixed additions from the table, u2*Q with a 4-bit window
 //                   (252 doublings + <= 64 additions), X.x == r checked
 //                   projectively (r*Z^2 == X, and (r+n)*Z^2 when r+n < p)
+//
+// Signing (validator/ecdsa/ecdsa.go:49-63, Signer.Sign) shares the table, the digest
+// kernel and the staging slots:
+//   k_ecdsa_sign    RFC 6979 nonce (common/hmac_drbg.hpp), k*G as <= 16 mixed
+//                   additions from the table, affine x (one inversion mod p),
+//                   r = x mod n, s = k^-1 (e + r d) (Fermat mod n), low-S flip
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
@@ -31,15 +37,19 @@
 #include <vector>
 
 #include "../../include/fts_gpu.h"
+#include "common/hmac_drbg.hpp"
 #include "common/sha256.hpp"
 #include "device/p256.hpp"
 #include "host/hip_owned.hpp"
 #include "host/host_pool.hpp"
+#include "host/prover.hpp"  // RngSource: the hedged mode's additional data
+#include "host/sign_encode.hpp"
 
 using namespace p256;
 using fts::DevBuf;
 using fts::Event;
 using fts::PinBuf;
+using fts::SecretWipe;
 using fts::SlotRing;
 using fts::Stream;
 
@@ -185,6 +195,72 @@ __global__ __launch_bounds__(256) void k_ecdsa_verify(int n, const uint32_t* __r
   status[i] = ok ? FTS_OK : FTS_E_SIG_INVALID;
 }
 
+
+// floor(n / 2), little-endian limbs (the low-S bound)
+__device__ constexpr uint32_t HALF_N[8] = {0x7e3192a8u, 0x79dce561u, 0xd38bcf42u, 0xde737d56u,
+                                           0xffffffffu, 0x7fffffffu, 0x80000000u, 0x7fffffffu};
+constexpr int SREC_WORDS = 16;  // d[8] extra[8], big-endian words (the HMAC input order)
+
+// One signature per lane.  srec: private scalar and additional data; e: the digest
+// as k_ecdsa_digest leaves it (little-endian limbs); rs <- r[8] s[8], little-endian
+// limbs.  Lanes whose status is not FTS_OK (rejected keys) write nothing.
+// Not constant time: table rows are gathered by nonce digits, zero digits skipped.
+template <bool HEDGED>
+__global__ __launch_bounds__(256, 2) void k_ecdsa_sign(int n, const uint32_t* __restrict__ srec,
+                                                    const uint32_t* __restrict__ e,
+                                                    const uint32_t* __restrict__ table,
+                                                    const int32_t* __restrict__ status,
+                                                    uint32_t* __restrict__ rs) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n || status[i] != FTS_OK) return;
+  const uint32_t* S = srec + (size_t)i * SREC_WORDS;
+  uint32_t x[8], h1[8], dl[8], ev[8];
+#pragma unroll
+  for (int k = 0; k < 8; k++) x[k] = S[k], dl[7 - k] = S[k], ev[k] = e[(size_t)i * 8 + k], h1[7 - k] = ev[k];
+  fts::Rfc6979 g;
+  if (HEDGED) {
+    uint32_t ex[8];
+#pragma unroll
+    for (int k = 0; k < 8; k++) ex[k] = S[8 + k];
+    g.init<true>(x, h1, ex);
+  } else {
+    g.init<false>(x, h1, nullptr);
+  }
+  const Fn dm = to_mont(load<NM>(dl));
+  Fn em = load<NM>(ev);  // e mod n (e < 2^256 < 2n)
+  cond_sub(em, 0);
+  // RFC 6979 section 3.2 step h: candidates until r != 0 and s != 0
+  for (;;) {
+    uint32_t kb[8], kl[8];
+    g.next(kb);  // 1 <= k < n
+#pragma unroll
+    for (int k = 0; k < 8; k++) kl[k] = kb[7 - k];
+    PJ acc = pj_inf();
+    for (int w = 0; w < FB_NW; w++) {
+      const uint32_t d = (kl[(w * FB_W) >> 5] >> ((w * FB_W) & 31)) & (uint32_t)(FB_ND - 1);
+      if (d) {
+        const uint32_t* t = table + ((size_t)w * FB_ND + d) * 16;
+        acc = pj_madd(acc, load<PM>(t), load<PM>(t + 8));
+      }
+    }
+    // k G != O for 0 < k < n.  r = x mod n: one subtraction (p < 2n)
+    const Fp zi = inv(acc.z);
+    const Fp ax = from_mont(mul(acc.x, sqr(zi)));
+    Fn r = load<NM>(ax.v);
+    cond_sub(r, 0);
+    if (is_zero(r)) continue;
+    // s = k^-1 (e + r d): a Montgomery-form factor times a plain one is plain
+    const Fn ki = inv(to_mont(load<NM>(kl)));
+    Fn sv = mul(ki, add(mul(dm, r), em));
+    if (is_zero(sv)) continue;
+    if (lt256(HALF_N, sv.v)) sv = sub(Fn{}, sv);  // ToLowS
+    uint32_t* out = rs + (size_t)i * 16;
+#pragma unroll
+    for (int k = 0; k < 8; k++) out[k] = r.v[k], out[8 + k] = sv.v[k];
+    return;
+  }
+}
+
 // ------------------------------------------------------------------- host
 
 // n and floor(n/2) as big-endian bytes
@@ -250,6 +326,7 @@ struct Slot {
   PinBuf h_stage;   // pinned host staging
   Event ev[3];
   float ms[2] = {0.f, 0.f};
+  float sign_ms[2] = {0.f, 0.f};
 };
 struct DevState {
   SlotRing<Slot, NSLOT> ring;  // its lock also guards init, init_err and ms
@@ -257,6 +334,7 @@ struct DevState {
   int init_err = 0;  // a failed initialisation is cached (no re-allocation on every retry)
   DevBuf d_table;
   float ms[2] = {0.f, 0.f};  // k_ecdsa_digest, k_ecdsa_verify of the last finished call
+  float sign_ms[2] = {0.f, 0.f};  // k_ecdsa_digest, k_ecdsa_sign of the last finished signing call
 };
 // never destroyed: its owners would release streams and memory during static
 // destruction, when the HIP runtime may already be gone
@@ -269,6 +347,36 @@ DevState& dev_state(int device) {
   do {                                          \
     if ((x) != hipSuccess) return FTS_API_EDEVICE; \
   } while (0)
+
+
+// the device's table, streams and events, created by the first call (verify or sign)
+int ensure_init(DevState& G, int device) {
+  std::lock_guard<std::mutex> l(G.ring.mu);
+  ECHK(hipSetDevice(device));
+  if (G.init_err) return G.init_err;
+  if (!G.init) {
+    // all or nothing: on any failure release what was created and cache the error
+    Stream s0;
+    bool ok = s0.create() == hipSuccess && G.d_table.reserve((size_t)FB_NW * FB_ND * 16 * 4);
+    if (ok) {
+      k_ecdsa_table<<<FB_NW * FB_ND / 256, 256, 0, s0>>>(G.d_table.as<uint32_t>());
+      ok = hipGetLastError() == hipSuccess && hipStreamSynchronize(s0) == hipSuccess;
+    }
+    for (auto& S : G.ring.slot) {
+      ok = ok && S.stream.create() == hipSuccess;
+      for (auto& e : S.ev) ok = ok && e.create() == hipSuccess;
+      S.d_table = G.d_table.as<uint32_t>();
+    }
+    if (!ok) {
+      for (auto& S : G.ring.slot) S = Slot();
+      G.d_table.release();
+      G.init_err = FTS_API_EDEVICE;
+      return G.init_err;
+    }
+    G.init = true;
+  }
+  return FTS_API_OK;
+}
 
 }  // namespace
 
@@ -335,32 +443,7 @@ int fts_ecdsa_verify_batch(int device, size_t n, const fts_ecdsa_item* items, in
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || device >= ndev) return FTS_API_EDEVICE;
   DevState& G = dev_state(device);
-  {
-    std::lock_guard<std::mutex> l(G.ring.mu);
-    ECHK(hipSetDevice(device));
-    if (G.init_err) return G.init_err;
-    if (!G.init) {
-      // all or nothing: on any failure release what was created and cache the error
-      Stream s0;
-      bool ok = s0.create() == hipSuccess && G.d_table.reserve((size_t)FB_NW * FB_ND * 16 * 4);
-      if (ok) {
-        k_ecdsa_table<<<FB_NW * FB_ND / 256, 256, 0, s0>>>(G.d_table.as<uint32_t>());
-        ok = hipGetLastError() == hipSuccess && hipStreamSynchronize(s0) == hipSuccess;
-      }
-      for (auto& S : G.ring.slot) {
-        ok = ok && S.stream.create() == hipSuccess;
-        for (auto& e : S.ev) ok = ok && e.create() == hipSuccess;
-        S.d_table = G.d_table.as<uint32_t>();
-      }
-      if (!ok) {
-        for (auto& S : G.ring.slot) S = Slot();
-        G.d_table.release();
-        G.init_err = FTS_API_EDEVICE;
-        return G.init_err;
-      }
-      G.init = true;
-    }
-  }
+  if (const int rc = ensure_init(G, device)) return rc;
   auto guard = G.ring.acquire([&G](Slot& S) { G.ms[0] = S.ms[0], G.ms[1] = S.ms[1]; });
   Slot& D = guard.slot();
   ECHK(hipSetDevice(device));
@@ -443,6 +526,136 @@ int fts_ecdsa_last_timings(int device, float* ms2) {
   std::lock_guard<std::mutex> l(G.ring.mu);
   ms2[0] = G.ms[0];
   ms2[1] = G.ms[1];
+  return FTS_API_OK;
+}
+
+int fts_ecdsa_sig_encode(const uint8_t* r32, const uint8_t* s32, uint8_t* out72, uint32_t* len) {
+  if (!r32 || !s32 || !out72 || !len) return FTS_API_EINVAL;
+  *len = fts::host::ecdsa_sig_der(r32, s32, out72);
+  return FTS_API_OK;
+}
+
+int fts_ecdsa_sign_batch(int device, size_t n, const fts_ecdsa_sign_item* items, int nonce_mode, uint64_t seed,
+                         uint8_t* sig, uint32_t* sig_len, int32_t* status) {
+  if (device < 0 || device >= 16 || n > (size_t)(1u << 24) || (n && (!items || !sig || !sig_len || !status)) ||
+      (nonce_mode != FTS_NONCE_RFC6979 && nonce_mode != FTS_NONCE_HEDGED))
+    return FTS_API_EINVAL;
+  if (n == 0) return FTS_API_OK;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || device >= ndev) return FTS_API_EDEVICE;
+  const bool hedged = nonce_mode == FTS_NONCE_HEDGED;
+  const fts::host::RngSource src(hedged ? seed : 0);
+  if (!src.ok) return FTS_API_EDEVICE;
+  DevState& G = dev_state(device);
+  if (const int rc = ensure_init(G, device)) return rc;
+  auto guard = G.ring.acquire([&G](Slot& S) { G.sign_ms[0] = S.sign_ms[0], G.sign_ms[1] = S.sign_ms[1]; });
+  Slot& D = guard.slot();
+  ECHK(hipSetDevice(device));
+  // staging: secrets (d | extra) | e | moff | mlen | status | r,s (device -> host) | messages
+  const size_t sec_b = n * SREC_WORDS * 4, e_b = n * 32, off_b = n * 8, len_b = n * 4, st_b = n * 4, rs_b = n * 64;
+  const size_t up = sec_b + e_b + off_b + len_b + st_b, tot = up + rs_b;
+  size_t mtot = 0;
+  for (size_t i = 0; i < n; i++) {
+    if (items[i].msg_len > 0xffffffffu || (items[i].msg_len && !items[i].msg)) return FTS_API_EINVAL;
+    mtot += items[i].msg_len;
+  }
+  const size_t need = tot + mtot;
+  if (D.h_stage.cap < need && !D.h_stage.reserve(need + need / 2)) return FTS_API_ENOMEM;
+  if (D.d_rec.cap < tot && !D.d_rec.reserve(tot + tot / 2)) return FTS_API_ENOMEM;
+  if (D.d_msg.cap < std::max<size_t>(mtot, 1) && !D.d_msg.reserve(mtot + mtot / 2 + 1)) return FTS_API_ENOMEM;
+  uint8_t* h = D.h_stage.as<uint8_t>();
+  uint8_t* const d_rec = D.d_rec.as<uint8_t>();
+  SecretWipe wipe(D.stream);
+  wipe.host = h, wipe.bytes = sec_b;
+  uint32_t* hsec = reinterpret_cast<uint32_t*>(h);
+  uint64_t* hoff = reinterpret_cast<uint64_t*>(h + sec_b + e_b);
+  uint32_t* hlen = reinterpret_cast<uint32_t*>(h + sec_b + e_b + off_b);
+  int32_t* hst = reinterpret_cast<int32_t*>(h + sec_b + e_b + off_b + len_b);
+  const uint32_t* hrs = reinterpret_cast<const uint32_t*>(h + up);
+  uint8_t* hm = h + tot;
+  {
+    uint64_t o = 0;
+    for (size_t i = 0; i < n; i++) hoff[i] = o, o += items[i].msg_len;
+  }
+  const size_t CH = 2048, nch = (n + CH - 1) / CH;
+  fts::host_parallel_for(nch, [&](size_t c) {
+    for (size_t i = c * CH; i < std::min(n, (c + 1) * CH); i++) {
+      const fts_ecdsa_sign_item& it = items[i];
+      uint32_t* R = hsec + i * SREC_WORDS;
+      static const uint8_t zero32[32] = {0};
+      // 0 < d < n, decided here: a rejected key never reaches the device
+      const bool good = it.d32 && memcmp(it.d32, zero32, 32) != 0 && cmp32(it.d32, kN) < 0;
+      hst[i] = good ? FTS_OK : FTS_E_SIGN_BADKEY;
+      for (int k = 0; k < 8; k++) {
+        R[k] = 0u;
+        if (good)
+          R[k] = ((uint32_t)it.d32[4 * k] << 24) | ((uint32_t)it.d32[4 * k + 1] << 16) |
+                 ((uint32_t)it.d32[4 * k + 2] << 8) | (uint32_t)it.d32[4 * k + 3];
+      }
+      if (hedged && good) {
+        fts::host::Rng rng = src.at(i);
+        for (int k = 0; k < 4; k++) {
+          const uint64_t v = rng.next();
+          R[8 + 2 * k] = (uint32_t)(v >> 32), R[9 + 2 * k] = (uint32_t)v;
+        }
+      } else {
+        for (int k = 8; k < 16; k++) R[k] = 0u;
+      }
+      hlen[i] = (uint32_t)it.msg_len;
+      if (it.msg_len) memcpy(hm + hoff[i], it.msg, it.msg_len);
+    }
+  });
+  uint32_t* dsec = reinterpret_cast<uint32_t*>(d_rec);
+  uint32_t* de = reinterpret_cast<uint32_t*>(d_rec + sec_b);
+  uint64_t* doff = reinterpret_cast<uint64_t*>(d_rec + sec_b + e_b);
+  uint32_t* dlen = reinterpret_cast<uint32_t*>(d_rec + sec_b + e_b + off_b);
+  int32_t* dst = reinterpret_cast<int32_t*>(d_rec + sec_b + e_b + off_b + len_b);
+  uint32_t* drs = reinterpret_cast<uint32_t*>(d_rec + up);
+  wipe.dev = d_rec;
+  ECHK(hipMemcpyAsync(d_rec, h, up, hipMemcpyHostToDevice, D.stream));
+  if (mtot) ECHK(hipMemcpyAsync(D.d_msg.p, hm, mtot, hipMemcpyHostToDevice, D.stream));
+  const int nb = (int)((n + 255) / 256);
+  ECHK(hipEventRecord(D.ev[0], D.stream));
+  k_ecdsa_digest<<<nb, 256, 0, D.stream>>>((int)n, D.d_msg.as<uint8_t>(), doff, dlen, dst, de);
+  ECHK(hipGetLastError());
+  ECHK(hipEventRecord(D.ev[1], D.stream));
+  if (hedged) k_ecdsa_sign<true><<<nb, 256, 0, D.stream>>>((int)n, dsec, de, D.d_table, dst, drs);
+  else k_ecdsa_sign<false><<<nb, 256, 0, D.stream>>>((int)n, dsec, de, D.d_table, dst, drs);
+  ECHK(hipGetLastError());
+  ECHK(hipEventRecord(D.ev[2], D.stream));
+  ECHK(hipMemsetAsync(d_rec, 0, sec_b, D.stream));
+  wipe.dev = nullptr;  // queued
+  ECHK(hipMemcpyAsync(h + up, drs, rs_b, hipMemcpyDeviceToHost, D.stream));
+  ECHK(hipStreamSynchronize(D.stream));
+  memset(h, 0, sec_b);
+  wipe.host = nullptr;
+  // DER into the caller's buffer (host pool)
+  fts::host_parallel_for(nch, [&](size_t c) {
+    for (size_t i = c * CH; i < std::min(n, (c + 1) * CH); i++) {
+      status[i] = hst[i];
+      sig_len[i] = 0;
+      if (hst[i] != FTS_OK) continue;
+      uint8_t r32[32], s32[32];
+      const uint32_t* R = hrs + i * 16;
+      for (int k = 0; k < 8; k++)
+        for (int b = 0; b < 4; b++) {
+          r32[4 * k + b] = (uint8_t)(R[7 - k] >> (24 - 8 * b));
+          s32[4 * k + b] = (uint8_t)(R[15 - k] >> (24 - 8 * b));
+        }
+      sig_len[i] = fts::host::ecdsa_sig_der(r32, s32, sig + i * FTS_ECDSA_SIG_MAX);
+    }
+  });
+  ECHK(hipEventElapsedTime(&D.sign_ms[0], D.ev[0], D.ev[1]));
+  ECHK(hipEventElapsedTime(&D.sign_ms[1], D.ev[1], D.ev[2]));
+  return FTS_API_OK;
+}
+
+int fts_ecdsa_sign_last_timings(int device, float* ms2) {
+  if (device < 0 || device >= 16 || !ms2) return FTS_API_EINVAL;
+  DevState& G = dev_state(device);
+  std::lock_guard<std::mutex> l(G.ring.mu);
+  ms2[0] = G.sign_ms[0];
+  ms2[1] = G.sign_ms[1];
   return FTS_API_OK;
 }
 

@@ -11,6 +11,7 @@
 //     that static destruction may already have torn down.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <string.h>
 #include <algorithm>
 #include <condition_variable>
 #include <mutex>
@@ -108,6 +109,24 @@ struct Event : Handle<hipEvent_t, hipEventDestroy> {
   hipError_t create(unsigned flags = hipEventDefault) {
     release();
     return hipEventCreateWithFlags(&h, flags);
+  }
+};
+
+// Wipes a signing call's secrets from its staging slot on every way out of the call:
+// the device region by a memset on the slot's stream (behind the last kernel), the
+// pinned region after the stream has drained.  A call that has queued the device
+// memset itself clears `dev`; one that has wiped the pinned region clears `host`.
+struct SecretWipe {
+  hipStream_t stream;
+  void* dev = nullptr;
+  void* host = nullptr;
+  size_t bytes = 0;
+  explicit SecretWipe(hipStream_t s) : stream(s) {}
+  SecretWipe(const SecretWipe&) = delete;
+  ~SecretWipe() {
+    if (dev) (void)hipMemsetAsync(dev, 0, bytes, stream);
+    if (dev || host) (void)hipStreamSynchronize(stream);
+    if (host) memset(host, 0, bytes);
   }
 };
 

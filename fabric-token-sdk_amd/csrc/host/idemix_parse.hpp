@@ -22,6 +22,9 @@ using fts::Span;
 // per-item record (words): c[8] s_sk[8] s_rnym[8] (plain LE limbs, c < r,
 // s mod r), nonce[8] (big-endian words, as hashed)
 constexpr int NREC = 32;
+// nym signing: per-item secrets sk[8] rnym[8] r_sk[8] r_r[8] (canonical LE limbs) nonce[8]
+// (big-endian words), and the device's answer c[8] s_sk[8] s_r[8] (canonical LE limbs)
+constexpr int NSREC = 40, NSOUT = 24;
 
 // ------------------------------------------------------------ identity record
 // bases of the issuer tables: HSk, HRand, HAttrs[0..3], g1

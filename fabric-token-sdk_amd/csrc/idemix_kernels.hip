@@ -23,6 +23,12 @@
 //       (2 x 16 mixed additions) + (r - c) Nym (GLV, glv.hpp), affine t,
 //       SHA-256 over the 164-byte prefix and the message (streamed from HBM
 //       as aligned words), HashToZr, the second 64-byte hash, c == c''.
+//
+// Signing (IBM/idemix NewNymSignature, reached from services/identity/idemix/crypto/id.go):
+//   k_nym_sign / k_nym_sign_fbn  t = r_sk HSk + r_r HRand (2 x 16 mixed additions from
+//       the same tables, no variable-base product), affine t, the verify kernels' hashed
+//       stream (restated, so that their code is untouched), c, s_sk = r_sk + c sk and
+//       s_r = r_r + c rnym mod r.  The nonces are drawn on the host.
 // The host side (handle, parser, staging) is api_idemix.cpp over host/idemix_parse.hpp.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -39,6 +45,8 @@
 
 using namespace fts;
 using idv::NREC;
+using idv::NSREC;
+using idv::NSOUT;
 
 namespace {
 
@@ -160,6 +168,85 @@ __global__ __launch_bounds__(256) void k_nym_verify(int n, const uint32_t* __res
 #pragma unroll
   for (int k = 0; k < 8; k++) diff |= c2.v[k] ^ R[k];
   status[i] = diff ? FTS_E_NYM_INVALID : FTS_OK;
+}
+
+// One BN254 nym signature per lane.  srec: sk, rnym, r_sk, r_r (canonical LE limbs)
+// and the nonce (big-endian words); out <- c, s_sk, s_r (canonical LE limbs).
+// Nym is decoded only to give a bad key the verifier's verdict.
+__global__ __launch_bounds__(256) void k_nym_sign(int n, const uint32_t* __restrict__ srec,
+                                                  const uint8_t* __restrict__ nym_raw,
+                                                  const uint32_t* __restrict__ msgw,
+                                                  const uint64_t* __restrict__ moff,  // word offsets
+                                                  const uint32_t* __restrict__ mlen,
+                                                  const uint32_t* __restrict__ tables,
+                                                  const uint32_t* __restrict__ ipk_hash,  // 8 BE words
+                                                  int32_t* __restrict__ status, uint32_t* __restrict__ out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n || status[i] != FTS_OK) return;
+  const uint32_t* S = srec + (size_t)i * NSREC;
+  G1A nym;
+  if (!decode_point(nym_raw + (size_t)i * 64, nym)) {
+    status[i] = FTS_E_NYM_BADKEY;
+    return;
+  }
+  // t = r_sk HSk + r_r HRand
+  G1J acc = g1j_identity();
+  fb_mul_acc(acc, tables, load_scalar(S + 16));
+  fb_mul_acc(acc, tables + FB_WORDS_PER_BASE, load_scalar(S + 24));
+  const G1A t = g1j_to_affine(acc);  // identity (both nonces zero) -> 64 zero bytes
+  uint32_t tw[16], nw[16], hw[8];
+  g1_mont_to_be_words(t.x, t.y, tw);
+  load_be_words(nym_raw + (size_t)i * 64, nw);
+#pragma unroll
+  for (int k = 0; k < 8; k++) hw[k] = ipk_hash[k];
+  const uint32_t* m = msgw + moff[i];
+  const uint32_t len = mlen[i];
+  const uint32_t nb = sha_blocks(164u + len);  // >= 3
+  uint32_t st[8], w[16];
+  sha256_init(st);
+  // "sign" t | t[15] Nym | Nym[15] ipk.Hash message (the stream of k_nym_verify)
+  w[0] = 0x7369676eu;
+#pragma unroll
+  for (int k = 1; k < 16; k++) w[k] = tw[k - 1];
+  sha256_compress(st, w);
+  w[0] = tw[15];
+#pragma unroll
+  for (int k = 1; k < 16; k++) w[k] = nw[k - 1];
+  sha256_compress(st, w);
+  w[0] = nw[15];
+#pragma unroll
+  for (int k = 1; k < 9; k++) w[k] = hw[k - 1];
+#pragma unroll
+  for (int k = 9; k < 16; k++) w[k] = stream_word(m, len, nb, 32 + k);
+  sha256_compress(st, w);
+  for (uint32_t blk = 3; blk < nb; blk++) {
+#pragma unroll
+    for (int k = 0; k < 16; k++) w[k] = stream_word(m, len, nb, 16 * blk + k);
+    sha256_compress(st, w);
+  }
+  // c = HashToZr(HashToZr(...) || nonce)
+  const Fr c1 = digest_to_fr(st);
+#pragma unroll
+  for (int k = 0; k < 8; k++) w[k] = c1.v[7 - k];
+#pragma unroll
+  for (int k = 0; k < 8; k++) w[8 + k] = S[32 + k];
+  sha256_init(st);
+  sha256_compress(st, w);
+  w[0] = 0x80000000u;
+#pragma unroll
+  for (int k = 1; k < 15; k++) w[k] = 0u;
+  w[15] = 512u;
+  sha256_compress(st, w);
+  const Fr c = digest_to_fr(st);
+  // s = r + c * secret: a Montgomery-form factor times a plain one is plain
+  const Fr cm = f_to_mont(c);
+  Fr sk, rn, rsk, rr;
+#pragma unroll
+  for (int k = 0; k < 8; k++) sk.v[k] = S[k], rn.v[k] = S[8 + k], rsk.v[k] = S[16 + k], rr.v[k] = S[24 + k];
+  const Fr s_sk = f_add(f_mul(cm, sk), rsk), s_r = f_add(f_mul(cm, rn), rr);
+  uint32_t* O = out + (size_t)i * NSOUT;
+#pragma unroll
+  for (int k = 0; k < 8; k++) O[k] = c.v[k], O[8 + k] = s_sk.v[k], O[16 + k] = s_r.v[k];
 }
 
 // ------------------------------------------------------------ FP256BN keys
@@ -395,6 +482,99 @@ __global__ __launch_bounds__(256) void k_nym_verify_fbn(int n, const uint32_t* _
   status[i] = diff ? FTS_E_NYM_INVALID : FTS_OK;
 }
 
+// One FP256BN nym signature per lane: srec and out as k_nym_sign, the region and nymxy
+// as k_nym_verify_fbn.
+__global__ __launch_bounds__(256) void k_nym_sign_fbn(int n, const uint32_t* __restrict__ srec,
+                                                      const uint8_t* __restrict__ nymxy,
+                                                      const uint32_t* __restrict__ region,
+                                                      const uint64_t* __restrict__ roff,  // word offsets
+                                                      const uint32_t* __restrict__ rlen,  // stream bytes
+                                                      const uint32_t* __restrict__ tables,
+                                                      int32_t* __restrict__ status, uint32_t* __restrict__ out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n || status[i] != FTS_OK) return;
+  const uint32_t* S = srec + (size_t)i * NSREC;
+  uint32_t pw[16];
+  load_be_words(nymxy + (size_t)i * 64, pw);
+  uint32_t nx[8], ny[8];
+#pragma unroll
+  for (int k = 0; k < 8; k++) nx[k] = pw[7 - k], ny[k] = pw[15 - k];
+  if (!p256::lt256(nx, fbn::PM::M) || !p256::lt256(ny, fbn::PM::M) ||
+      !fbn::on_curve(p256::to_mont(fbn::load<fbn::PM>(nx)), p256::to_mont(fbn::load<fbn::PM>(ny)))) {
+    status[i] = FTS_E_NYM_BADKEY;
+    return;
+  }
+  // t = r_sk HSk + r_r HRand: 2 x 16 mixed additions from the tables
+  fbn::PJ acc = fbn::pj_inf();
+#pragma unroll 1
+  for (int q = 0; q < 2; q++) {
+    const uint32_t* sc = S + 16 + 8 * q;
+    const uint32_t* tb = tables + (size_t)q * FBN_NW * FBN_ND * 16;
+    for (int w = 0; w < FBN_NW; w++) {
+      const uint32_t d = (sc[w >> 1] >> (16 * (w & 1))) & 0xffffu;
+      if (d) {
+        const uint32_t* t = tb + ((size_t)w * FBN_ND + d) * 16;
+        acc = fbn::pj_madd(acc, fbn::load<fbn::PM>(t), fbn::load<fbn::PM>(t + 8));
+      }
+    }
+  }
+  uint32_t tw[16];
+  if (fbn::is_zero(acc.z)) {
+#pragma unroll
+    for (int k = 0; k < 16; k++) tw[k] = 0u;  // t = O (both nonces zero): AMCL ToBytes of infinity
+    tw[15] = 1u;
+  } else {
+    const fbn::Fp zi = p256::inv(acc.z), zi2 = fbn::sqr(zi);
+    const fbn::Fp ax = p256::from_mont(fbn::mul(acc.x, zi2)), ay = p256::from_mont(fbn::mul(acc.y, fbn::mul(zi2, zi)));
+#pragma unroll
+    for (int k = 0; k < 8; k++) tw[k] = ax.v[7 - k], tw[8 + k] = ay.v[7 - k];
+  }
+  const uint32_t* m = region + roff[i];
+  const uint32_t ltot = rlen[i];
+  const uint32_t nb = sha_blocks(ltot);  // >= 3
+  uint32_t st[8], w[16];
+  sha256_init(st);
+  // "sign" 0x04 t[0..58] | t[59..63] then the host's bytes (the stream of k_nym_verify_fbn)
+  w[0] = 0x7369676eu;
+  w[1] = 0x04000000u | (tw[0] >> 8);
+#pragma unroll
+  for (int k = 2; k < 16; k++) w[k] = (tw[k - 2] << 24) | (tw[k - 1] >> 8);
+  sha256_compress(st, w);
+  w[0] = (tw[14] << 24) | (tw[15] >> 8);
+  w[1] = (tw[15] << 24) | (region_word(m, ltot, nb, 17) & 0x00ffffffu);
+#pragma unroll
+  for (int k = 2; k < 16; k++) w[k] = region_word(m, ltot, nb, 16 + k);
+  sha256_compress(st, w);
+  for (uint32_t blk = 2; blk < nb; blk++) {
+#pragma unroll
+    for (int k = 0; k < 16; k++) w[k] = region_word(m, ltot, nb, 16 * blk + k);
+    sha256_compress(st, w);
+  }
+  uint32_t c1[8];
+  digest_mod_rfbn(st, c1);
+#pragma unroll
+  for (int k = 0; k < 8; k++) w[k] = c1[7 - k];
+#pragma unroll
+  for (int k = 0; k < 8; k++) w[8 + k] = S[32 + k];
+  sha256_init(st);
+  sha256_compress(st, w);
+  w[0] = 0x80000000u;
+#pragma unroll
+  for (int k = 1; k < 15; k++) w[k] = 0u;
+  w[15] = 512u;
+  sha256_compress(st, w);
+  using Fz = p256::F<fbn::RM>;
+  Fz c;
+  digest_mod_rfbn(st, c.v);
+  // s = r + c * secret mod r: a Montgomery-form factor times a plain one is plain
+  const Fz cm = p256::to_mont(c);
+  const Fz s_sk = fbn::add(fbn::mul(cm, fbn::load<fbn::RM>(S)), fbn::load<fbn::RM>(S + 16));
+  const Fz s_r = fbn::add(fbn::mul(cm, fbn::load<fbn::RM>(S + 8)), fbn::load<fbn::RM>(S + 24));
+  uint32_t* O = out + (size_t)i * NSOUT;
+#pragma unroll
+  for (int k = 0; k < 8; k++) O[k] = c.v[k], O[8 + k] = s_sk.v[k], O[16 + k] = s_r.v[k];
+}
+
 // FP256BN issuer bases: plain big-endian ECP coordinates -> Montgomery, on-curve flags
 __global__ void k_fbn_bases(int nb, const uint32_t* __restrict__ plain, uint32_t* __restrict__ mont,
                             int32_t* __restrict__ ok) {
@@ -429,5 +609,13 @@ void launch_nym_verify(bool bn, int n, const uint32_t* rec, const uint8_t* nym, 
   const unsigned grid = (unsigned)((tile + 255) / 256);
   if (bn) k_nym_verify<<<grid, 256, 0, s>>>(n, rec, nym, msgw, moff, mlen, tables, ipk_hash, vtab, status, base, tile);
   else k_nym_verify_fbn<<<grid, 256, 0, s>>>(n, rec, nym, msgw, moff, mlen, tables, vtab, status, base, tile);
+}
+
+void launch_nym_sign(bool bn, int n, const uint32_t* srec, const uint8_t* nym, const uint32_t* msgw,
+                     const uint64_t* moff, const uint32_t* mlen, const uint32_t* tables, const uint32_t* ipk_hash,
+                     int32_t* status, uint32_t* out, hipStream_t s) {
+  const unsigned grid = (unsigned)((n + 255) / 256);
+  if (bn) k_nym_sign<<<grid, 256, 0, s>>>(n, srec, nym, msgw, moff, mlen, tables, ipk_hash, status, out);
+  else k_nym_sign_fbn<<<grid, 256, 0, s>>>(n, srec, nym, msgw, moff, mlen, tables, status, out);
 }
 }  // namespace fts

@@ -46,6 +46,12 @@ FTS_E_AUDIT_EID_MISMATCH = 30
 FTS_E_AUDIT_NO_RHNYM = 31
 FTS_E_AUDIT_RH_POINT = 32
 FTS_E_AUDIT_RH_MISMATCH = 33
+FTS_E_SIGN_BADKEY = 34
+# signing (include/fts_gpu.h)
+FTS_ECDSA_SIG_MAX = 72
+FTS_NYM_SIG_LEN = 136
+FTS_NONCE_RFC6979 = 0
+FTS_NONCE_HEDGED = 1
 # mathlib CurveID of idemix issuer keys
 FTS_CURVE_FP256BN_AMCL = 0
 FTS_CURVE_BN254 = 1
@@ -74,6 +80,8 @@ EXPORTED = [
     "fts_ctx_table_info", "fts_table_cache_stats",
     "fts_token_commit_batch_gpu", "fts_token_commit_batch_width", "fts_transfer_generate", "fts_issue_generate",
     "fts_transfer_generate_batch_gpu", "fts_issue_generate_batch_gpu",
+    "fts_ecdsa_sign_batch", "fts_ecdsa_sig_encode", "fts_ecdsa_sign_last_timings",
+    "fts_nym_sign_batch", "fts_nym_sign_last_timings",
 ]
 
 
@@ -116,6 +124,15 @@ class TokenOpening(C.Structure):
 class EcdsaItem(C.Structure):
     _fields_ = [("msg", C.c_void_p), ("msg_len", C.c_size_t), ("sig", C.c_void_p), ("sig_len", C.c_size_t),
                 ("pk64", C.c_void_p)]
+
+
+class EcdsaSignItem(C.Structure):
+    _fields_ = [("msg", C.c_void_p), ("msg_len", C.c_size_t), ("d32", C.c_void_p)]
+
+
+class NymSignItem(C.Structure):
+    _fields_ = [("sk32", C.c_void_p), ("rnym32", C.c_void_p), ("nym", C.c_void_p), ("nym_len", C.c_size_t),
+                ("msg", C.c_void_p), ("msg_len", C.c_size_t)]
 
 
 class NymItem(C.Structure):
@@ -245,6 +262,12 @@ def _load():
         "fts_issue_generate": ([P, C.POINTER(GenAction), C.c_uint64, C.POINTER(GenResult)], C.c_int),
         "fts_transfer_generate_batch_gpu": ([P, S, C.POINTER(GenAction), C.c_uint64, C.POINTER(GenResult)], C.c_int),
         "fts_issue_generate_batch_gpu": ([P, S, C.POINTER(GenAction), C.c_uint64, C.POINTER(GenResult)], C.c_int),
+        "fts_ecdsa_sign_batch": ([C.c_int, S, C.POINTER(EcdsaSignItem), C.c_int, C.c_uint64, P, C.POINTER(C.c_uint32),
+                                  I32P], C.c_int),
+        "fts_ecdsa_sig_encode": ([U8P, U8P, P, C.POINTER(C.c_uint32)], C.c_int),
+        "fts_ecdsa_sign_last_timings": ([C.c_int, C.POINTER(C.c_float)], C.c_int),
+        "fts_nym_sign_batch": ([P, S, C.POINTER(NymSignItem), C.c_uint64, P, I32P], C.c_int),
+        "fts_nym_sign_last_timings": ([P, C.POINTER(C.c_float)], C.c_int),
     }
     for name, (args, res) in sig.items():
         try:

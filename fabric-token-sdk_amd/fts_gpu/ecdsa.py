@@ -1,5 +1,5 @@
 """ECDSA P-256 owner signatures on the device (libfts_gpu.so
-``fts_ecdsa_verify_batch``; include/fts_gpu.h).
+``fts_ecdsa_verify_batch``, ``fts_ecdsa_sign_batch``; include/fts_gpu.h).
 
 Mirrors validator/ecdsa/ecdsa.go:69-113:
 
@@ -9,6 +9,11 @@ Mirrors validator/ecdsa/ecdsa.go:69-113:
 * ``verify_batch(items, device)`` is the batched form a validator uses for
   all owner signatures of many requests (TransferSignatureValidate,
   validator/validator_transfer.go:29-62, checks one per input).
+
+Signing mirrors ecdsa.go:49-63: ``Signer(d).Sign(message)`` and the batched
+``sign_batch(msgs, keys)`` return low-S DER signatures whose nonce is RFC 6979
+(``mode="rfc6979"``) or RFC 6979 with per-item additional data (``"hedged"``, the
+default), derived on the device; private keys are ints or 32 big-endian bytes.
 
 Public keys are ``(x, y)`` ints, 64-byte X||Y, or the DER SubjectPublicKeyInfo
 / PEM "PUBLIC KEY" that ``Verifier.Serialize`` wraps (ecdsa.go:115-150).
@@ -21,6 +26,10 @@ import numpy as np
 
 from . import _lib as L
 from ._lib import FTS_OK, FTS_E_SIG_MALFORMED, FTS_E_SIG_NOT_LOW_S, FTS_E_SIG_INVALID  # noqa: F401
+from ._lib import FTS_E_SIGN_BADKEY, FTS_NONCE_RFC6979, FTS_NONCE_HEDGED  # noqa: F401
+from ._lib import FTS_SEED_OS_RANDOM as OS_RANDOM
+
+_MODES = {"rfc6979": FTS_NONCE_RFC6979, "hedged": FTS_NONCE_HEDGED}
 
 
 class SignatureError(Exception):
@@ -120,6 +129,76 @@ def last_timings(device=0):
     ms = (C.c_float * 2)()
     L.check("fts_ecdsa_last_timings", L.lib.fts_ecdsa_last_timings(int(device), ms))
     return {"k_ecdsa_digest": ms[0], "k_ecdsa_verify": ms[1]}
+
+
+def _d32(d):
+    if isinstance(d, int):
+        # out-of-range ints still reach the library, which rejects them per item
+        return (d & ((1 << 256) - 1)).to_bytes(32, "big") if 0 <= d < (1 << 256) else b"\xff" * 32
+    d = bytes(d)
+    if len(d) != 32:
+        raise ValueError("a private key is an int or 32 big-endian bytes")
+    return d
+
+
+def sig_encode(r, s):
+    """utils.MarshalECDSASignature(r, s): minimal DER (host only)."""
+    out, n = (C.c_uint8 * L.FTS_ECDSA_SIG_MAX)(), C.c_uint32(0)
+    L.check("fts_ecdsa_sig_encode",
+            L.lib.fts_ecdsa_sig_encode(r.to_bytes(32, "big"), s.to_bytes(32, "big"), out, C.byref(n)))
+    return bytes(out[:n.value])
+
+
+def sign_batch(msgs, keys, device=0, mode="hedged", seed=OS_RANDOM, return_status=False):
+    """Sign msgs[i] under keys[i] in one device pass -> list of DER signatures
+    (``b""`` for a key outside [1, n-1]; with ``return_status`` also the int32 statuses).
+    mode: "hedged" (RFC 6979 section 3.6, additional data from `seed`; OS_RANDOM = the
+    secure source) or "rfc6979" (deterministic, `seed` ignored)."""
+    n = len(msgs)
+    if len(keys) != n:
+        raise ValueError("msgs and keys must have the same length")
+    if mode not in _MODES:
+        raise ValueError("mode is 'hedged' or 'rfc6979'")
+    st = np.zeros(n, dtype=np.int32)
+    if n == 0:
+        return ([], st) if return_status else []
+    keep = [(bytes(m), _d32(d)) for m, d in zip(msgs, keys)]
+    items = (L.EcdsaSignItem * n)()
+    for i, (m, d) in enumerate(keep):
+        items[i].msg = C.cast(C.c_char_p(m), C.c_void_p)
+        items[i].msg_len = len(m)
+        items[i].d32 = C.cast(C.c_char_p(d), C.c_void_p)
+    sig = np.zeros(n * L.FTS_ECDSA_SIG_MAX, dtype=np.uint8)
+    ln = np.zeros(n, dtype=np.uint32)
+    L.check("fts_ecdsa_sign_batch",
+            L.lib.fts_ecdsa_sign_batch(int(device), n, items, _MODES[mode], int(seed) & ((1 << 64) - 1),
+                                       sig.ctypes.data, ln.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                       st.ctypes.data_as(C.POINTER(C.c_int32))))
+    raw = sig.tobytes()
+    out = [raw[i * L.FTS_ECDSA_SIG_MAX:i * L.FTS_ECDSA_SIG_MAX + int(ln[i])] for i in range(n)]
+    return (out, st) if return_status else out
+
+
+def sign_last_timings(device=0):
+    """{kernel: ms} of the last signing call on `device` (HIP events)."""
+    ms = (C.c_float * 2)()
+    L.check("fts_ecdsa_sign_last_timings", L.lib.fts_ecdsa_sign_last_timings(int(device), ms))
+    return {"k_ecdsa_digest": ms[0], "k_ecdsa_sign": ms[1]}
+
+
+class Signer:
+    """ecdsa.Signer{SK} (validator/ecdsa/ecdsa.go:38-63): Sign returns the low-S DER
+    signature of SHA-256(message)."""
+
+    def __init__(self, d, device=0, mode="hedged", seed=OS_RANDOM):
+        self.d32 = _d32(d)
+        self.device, self.mode, self.seed = device, mode, seed
+
+    def Sign(self, message_):
+        sigs, st = sign_batch([message_], [self.d32], self.device, self.mode, self.seed, return_status=True)
+        if int(st[0]) != FTS_OK:
+            raise SignatureError(message(int(st[0])), int(st[0]))
+        return sigs[0]
 
 
 class Verifier:

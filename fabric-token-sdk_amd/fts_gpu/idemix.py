@@ -9,6 +9,10 @@ Mirrors services/identity/idemix/crypto/id.go:145-161:
   a validator uses for the owner signatures of idemix-owned inputs
   (TransferSignatureValidate, validator/validator_transfer.go:29-62).
 
+Signing: ``IssuerKey.sign_batch(sks, rnyms, nyms, msgs)`` and
+``NymSigner(issuer_key, sk, rnym, nym).Sign(message)`` produce the NymSignature
+protos that the verifiers above accept (k_nym_sign / k_nym_sign_fbn).
+
 The issuer key is the idemix IssuerPublicKey proto a zkatdlog PublicParams
 carries, on BN254 (the tokengen key of zkatdlog_pp.json) or FP256BN_AMCL (the
 validator's test keys).  There is no CPU fallback: every verdict comes from
@@ -25,6 +29,8 @@ from ._lib import (FTS_E_ID_MALFORMED, FTS_E_ID_BADNYM, FTS_E_ID_NO_EIDNYM, FTS_
 from ._lib import (FTS_E_AUDIT_MALFORMED, FTS_E_AUDIT_NO_EIDNYM, FTS_E_AUDIT_EID_POINT,  # noqa: F401
                    FTS_E_AUDIT_EID_MISMATCH, FTS_E_AUDIT_NO_RHNYM, FTS_E_AUDIT_RH_POINT, FTS_E_AUDIT_RH_MISMATCH)
 from ._lib import FTS_CURVE_BN254, FTS_CURVE_FP256BN_AMCL  # noqa: F401
+from ._lib import FTS_E_SIGN_BADKEY, FTS_NYM_SIG_LEN  # noqa: F401
+from ._lib import FTS_SEED_OS_RANDOM as OS_RANDOM
 
 
 class SignatureError(Exception):
@@ -128,6 +134,61 @@ class IssuerKey:
         ms = C.c_float()
         L.check("fts_nym_last_timings", L.lib.fts_nym_last_timings(self.h, C.byref(ms)))
         return ms.value
+
+    def sign_batch(self, sks, rnyms, nyms, msgs, seed=OS_RANDOM, return_status=False):
+        """n nym signatures in one device pass -> list of 136-byte NymSignature protos
+        (``b""`` for a rejected item; with ``return_status`` also the int32 statuses).
+        sks / rnyms: ints or 32 big-endian bytes below the curve's r; nyms: G1.Bytes() of
+        Nym = HSk^sk HRand^rnym.  seed: OS_RANDOM = the secure source, else test-only."""
+        n = len(msgs)
+        if not (len(sks) == len(rnyms) == len(nyms) == n):
+            raise ValueError("sks, rnyms, nyms and msgs must have the same length")
+        st = np.zeros(n, dtype=np.int32)
+        if n == 0:
+            return ([], st) if return_status else []
+
+        def z32(v):
+            if isinstance(v, int):
+                return v.to_bytes(32, "big") if 0 <= v < (1 << 256) else b"\xff" * 32
+            v = bytes(v)
+            if len(v) != 32:
+                raise ValueError("a secret is an int or 32 big-endian bytes")
+            return v
+        keep = [(z32(a), z32(b), bytes(c), bytes(d)) for a, b, c, d in zip(sks, rnyms, nyms, msgs)]
+        items = (L.NymSignItem * n)()
+        for i, (a, b, c, d) in enumerate(keep):
+            items[i].sk32 = C.cast(C.c_char_p(a), C.c_void_p)
+            items[i].rnym32 = C.cast(C.c_char_p(b), C.c_void_p)
+            items[i].nym = C.cast(C.c_char_p(c), C.c_void_p)
+            items[i].nym_len = len(c)
+            items[i].msg = C.cast(C.c_char_p(d), C.c_void_p)
+            items[i].msg_len = len(d)
+        sig = np.zeros(n * FTS_NYM_SIG_LEN, dtype=np.uint8)
+        L.check("fts_nym_sign_batch",
+                L.lib.fts_nym_sign_batch(self.h, n, items, int(seed) & ((1 << 64) - 1), sig.ctypes.data,
+                                         st.ctypes.data_as(C.POINTER(C.c_int32))))
+        raw = sig.tobytes()
+        out = [raw[i * FTS_NYM_SIG_LEN:(i + 1) * FTS_NYM_SIG_LEN] if st[i] == FTS_OK else b"" for i in range(n)]
+        return (out, st) if return_status else out
+
+    def last_sign_kernel_ms(self):
+        ms = C.c_float()
+        L.check("fts_nym_sign_last_timings", L.lib.fts_nym_sign_last_timings(self.h, C.byref(ms)))
+        return ms.value
+
+
+class NymSigner:
+    """The nym signer of services/identity/idemix/crypto/id.go: Sign returns the
+    NymSignature proto over `message` for the pseudonym (sk, rnym, nym)."""
+
+    def __init__(self, issuer_key, sk, rnym, nym_pk, seed=OS_RANDOM):
+        self.ipk, self.sk, self.rnym, self.nym, self.seed = issuer_key, sk, rnym, bytes(nym_pk), seed
+
+    def Sign(self, message_):
+        sigs, st = self.ipk.sign_batch([self.sk], [self.rnym], [self.nym], [message_], self.seed, return_status=True)
+        if int(st[0]) != FTS_OK:
+            raise SignatureError(message(int(st[0])), int(st[0]))
+        return sigs[0]
 
 
 class NymSignatureVerifier:

@@ -88,7 +88,10 @@ enum fts_status {
   FTS_E_AUDIT_EID_MISMATCH = 30, /* "eid nym does not match" */
   FTS_E_AUDIT_NO_RHNYM = 31,     /* "no RhNym provided" */
   FTS_E_AUDIT_RH_POINT = 32,     /* RhNym does not decode */
-  FTS_E_AUDIT_RH_MISMATCH = 33   /* "rh nym does not match" */
+  FTS_E_AUDIT_RH_MISMATCH = 33,  /* "rh nym does not match" */
+  /* signing (fts_ecdsa_sign_batch, fts_nym_sign_batch): no reference string, a signer holding
+   * such a key cannot exist there */
+  FTS_E_SIGN_BADKEY = 34         /* private scalar out of range: ECDSA d = 0 or d >= n; nym sk or rnym >= r */
 };
 
 /* ---- API return codes ---- */
@@ -553,6 +556,41 @@ int fts_p256_pubkey_from_pkix(const uint8_t* der, size_t len, uint8_t* pk64);
  * ms2[0] = k_ecdsa_digest, ms2[1] = k_ecdsa_verify. */
 int fts_ecdsa_last_timings(int device, float* ms2);
 
+/* ---- ECDSA P-256 signing (x509 owners) ----
+ * Per item what ecdsa.Signer.Sign(message) returns (validator/ecdsa/ecdsa.go:49-63): the
+ * digest is SHA-256 of the message, s is normalised to s <= n/2 (ToLowS) and (r, s) is written
+ * as utils.MarshalECDSASignature does (minimal DER).  The nonce is NOT Go's (crypto/ecdsa.Sign is
+ * randomised): it is RFC 6979 HMAC-DRBG over SHA-256, derived on the device, so signature
+ * values differ from a Go signer's and every verifier accepts them.
+ *   FTS_NONCE_RFC6979  deterministic; `seed` is ignored
+ *   FTS_NONCE_HEDGED   RFC 6979 section 3.6: 32 bytes of additional data per item, the four
+ *                      Rng::next() words of RngSource(seed).at(i), each big-endian
+ *                      (FTS_SEED_OS_RANDOM: the secure ChaCha20 source, as for the provers)
+ * In neither mode can two different messages under one key share a nonce, whatever the seed.
+ * The kernels are not hardened against timing or cache side channels: sign on a device the
+ * key owner controls.  The private scalars are wiped from the staging slot before it is
+ * released. */
+typedef struct {
+  const uint8_t* msg; /* message; SHA-256 is computed on the device */
+  size_t msg_len;
+  const uint8_t* d32; /* private scalar, 32 B big-endian, 0 < d < n */
+} fts_ecdsa_sign_item;
+#define FTS_ECDSA_SIG_MAX 72
+#define FTS_NONCE_RFC6979 0
+#define FTS_NONCE_HEDGED 1
+/* sig: n * FTS_ECDSA_SIG_MAX bytes, signature i at sig + i * FTS_ECDSA_SIG_MAX, sig_len[i] long.
+ * status[i] <- FTS_OK | FTS_E_SIGN_BADKEY (d = 0, d >= n or a NULL d32: sig_len[i] = 0; the other
+ * items are not affected).  Argument errors, n = 0, n > 2^24 and a missing device as
+ * fts_ecdsa_verify_batch; a nonce_mode other than the two above is FTS_API_EINVAL. */
+int fts_ecdsa_sign_batch(int device, size_t n, const fts_ecdsa_sign_item* items, int nonce_mode, uint64_t seed,
+                         uint8_t* sig, uint32_t* sig_len, int32_t* status);
+/* Host-only: (r, s), 32 B big-endian each -> minimal DER in out72 (at most FTS_ECDSA_SIG_MAX
+ * bytes), *len <- its length. */
+int fts_ecdsa_sig_encode(const uint8_t* r32, const uint8_t* s32, uint8_t* out72, uint32_t* len);
+/* HIP-event durations (ms) of the last fts_ecdsa_sign_batch on `device`:
+ * ms2[0] = k_ecdsa_digest, ms2[1] = k_ecdsa_sign (the nonce derivation runs inside it). */
+int fts_ecdsa_sign_last_timings(int device, float* ms2);
+
 /* ---- idemix pseudonym signatures (idemix owner identities, BN254 issuer keys) ----
  * Replaces, per item, crypto.NymSignatureVerifier.Verify(message, sigma)
  * (services/identity/idemix/crypto/id.go:145-161 -> IBM/idemix NymSignature.Ver),
@@ -585,6 +623,33 @@ int fts_nym_verify_batch(fts_idemix_ipk* ipk, size_t n, const fts_nym_item* item
 int fts_idemix_identity_nym(const uint8_t* id, size_t len, const uint8_t** nym, size_t* nym_len);
 /* HIP-event duration (ms) of k_nym_verify in the last finished fts_nym_verify_batch on `ipk`. */
 int fts_nym_last_timings(fts_idemix_ipk* ipk, float* ms);
+
+/* ---- idemix pseudonym signing ----
+ * Per item what the nym signer of services/identity/idemix/crypto/id.go produces (IBM/idemix
+ * NewNymSignature), with the randomness of RngSource(seed).at(i) drawn on the host in the order
+ * nonce, r_sk, r_r (uniform below the key's r; FTS_SEED_OS_RANDOM: the secure source):
+ *   t = r_sk HSk + r_r HRand;  c = HashToZr(HashToZr("sign" || t || Nym || ipk.Hash || msg) || nonce);
+ *   s_sk = r_sk + c sk;  s_r = r_r + c rnym  (mod r)
+ * written as the NymSignature proto (proof_c, proof_s_sk, proof_s_r_nym, nonce: 4 x 34 bytes).
+ * Not hardened against timing or cache side channels, secrets wiped from the slot before it is
+ * released: as fts_ecdsa_sign_batch. */
+typedef struct {
+  const uint8_t* sk32;   /* user secret, 32 B big-endian, < r */
+  const uint8_t* rnym32; /* nym randomness, 32 B big-endian, < r */
+  const uint8_t* nym;    /* G1.Bytes() of Nym = HSk^sk HRand^rnym (64 B / 65 B, as fts_nym_item) */
+  size_t nym_len;
+  const uint8_t* msg;
+  size_t msg_len;
+} fts_nym_sign_item;
+#define FTS_NYM_SIG_LEN 136
+/* sig: n * FTS_NYM_SIG_LEN bytes.  status[i] <- FTS_OK | FTS_E_SIGN_BADKEY (sk or rnym >= r, or
+ * NULL) | FTS_E_NYM_BADKEY (nym of the wrong length / form or not on the curve, as in
+ * verification); a rejected item's 136 bytes are zero and the other items are not affected.
+ * FTS_API_EINVAL for a NULL handle or argument, n > 2^24 or a NULL msg with a length. */
+int fts_nym_sign_batch(fts_idemix_ipk* ipk, size_t n, const fts_nym_sign_item* items, uint64_t seed, uint8_t* sig,
+                       int32_t* status);
+/* HIP-event duration (ms) of k_nym_sign / k_nym_sign_fbn in the last finished fts_nym_sign_batch. */
+int fts_nym_sign_last_timings(fts_idemix_ipk* ipk, float* ms);
 
 /* ---- idemix identity validity (idemix half) ----
  * Replaces the validity check of idemix Deserializer.Deserialize(raw, true)
