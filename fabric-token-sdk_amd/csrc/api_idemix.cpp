@@ -142,6 +142,13 @@ struct fts_idemix_idv {
   }
 };
 
+// what a credential handle borrows from its identity verifier (api_idgen.cpp)
+namespace idv {
+IdvView idv_view(const fts_idemix_idv* k) {
+  return IdvView{k->device, k->curve, k->d_tables.as<uint32_t>(), k->d_hash.as<uint32_t>()};
+}
+}  // namespace idv
+
 extern "C" {
 
 // ---------------------------------------------------------------------------

@@ -131,6 +131,7 @@ void launch_nym_sign(bool bn, int n, const uint32_t* srec, const uint8_t* nym, c
 }  // namespace fts
 
 // ---- idemix_identity_<cv>.hip, idemix_pairing_<cv>.hip, idemix_bp_<cv>.hip, cv = bn | fbn (device/idv_kernels.hpp)
+struct fts_idemix_idv;
 namespace idv {
 struct BnCurve;
 struct FbnCurve;
@@ -182,4 +183,32 @@ size_t bp_scratch_words(size_t n);
 void launch_idv_audit(bool bn, int n, const uint8_t* pts, const uint32_t* rnd, const uint32_t* attrw,
                       const uint64_t* aoff, const uint32_t* alen, const int32_t* pre, const int32_t* rh_pre,
                       const uint32_t* tables, int32_t* half_st, hipStream_t s);
+
+// ---- idemix_idgen_<cv>.hip (device/idgen_kernels.hpp): identity generation
+// per identity: draws staged (IDG_ND x 8 words), scalar slots of k_idg_prep, output points
+// (Jacobian), words written back; per credential: secrets (sk E S attrs), constant points + mask
+constexpr int IDG_ND = 18, IDG_NPROD = 19, IDG_NSC = IDG_NPROD + 2, IDG_NPT = 11, IDG_OUT_WORDS = 6 * 16 + 13 * 8;
+constexpr int IDG_SEC_WORDS = 7 * 8, IDG_CPT_WORDS = 3 * 16 + 1;
+struct GenChain {
+  hipStream_t s;
+  hipEvent_t ev_mid;  // recorded between k_idg_points and k_idg_finish
+  int n;
+  const uint32_t *draws, *sec, *cpt;  // [n][IDG_ND][8]; the credential's
+  uint32_t *sc, *pts, *pre;           // [IDG_NSC][n][8]; [IDG_NPT][24][n]; [IDG_NPT * 8][n]
+  uint8_t* msg;                       // [MSG_MAX][n]
+  const uint32_t *itab, *ctab, *hash;  // issuer tables, the tables of A and B, ipk.Hash
+  uint32_t* out;                      // [n][IDG_OUT_WORDS]
+  const int32_t* st;
+};
+// api_idemix.cpp: the verifier handle's device, curve, seven fixed-base tables and ipk.Hash words
+struct IdvView {
+  int device, curve;
+  const uint32_t *tables, *hash;
+};
+IdvView idv_view(const ::fts_idemix_idv* k);
+template <class CV>
+void launch_idgen_cred(const uint32_t* tables, const uint32_t* ab, const uint32_t* sec, uint32_t* cpt, int32_t* ok,
+                       hipStream_t s);
+template <class CV>
+hipError_t launch_idgen(const GenChain& c);
 }  // namespace idv

@@ -1,0 +1,10 @@
+// BN254 instances of the identity-generation kernels (device/idgen_kernels.hpp).
+#include "device/idgen_kernels.hpp"
+
+namespace idv {
+
+template void launch_idgen_cred<BnCurve>(const uint32_t*, const uint32_t*, const uint32_t*, uint32_t*, int32_t*,
+                                         hipStream_t);
+template hipError_t launch_idgen<BnCurve>(const GenChain&);
+
+}  // namespace idv

@@ -13,6 +13,10 @@ Signing: ``IssuerKey.sign_batch(sks, rnyms, nyms, msgs)`` and
 ``NymSigner(issuer_key, sk, rnym, nym).Sign(message)`` produce the NymSignature
 protos that the verifiers above accept (k_nym_sign / k_nym_sign_fbn).
 
+Identities: ``IdentityVerifier`` checks owner identities and matches audit info against
+them; ``Credential(verifier, cred, sk).generate(n)`` produces them on the device
+(KeyManager.Identity, services/identity/idemix/km.go:173-290).
+
 The issuer key is the idemix IssuerPublicKey proto a zkatdlog PublicParams
 carries, on BN254 (the tokengen key of zkatdlog_pp.json) or FP256BN_AMCL (the
 validator's test keys).  There is no CPU fallback: every verdict comes from
@@ -331,6 +335,183 @@ class IdentityError(Exception):
     def __init__(self, msg, status):
         super().__init__(msg)
         self.status = status
+
+
+def _pb_top_fields(raw):
+    """(field, wire type, value) of a proto's top level: varints and length-delimited
+    fields only (what IdemixSignerConfig carries)"""
+    out, i, n = [], 0, len(raw)
+
+    def varint():
+        nonlocal i
+        v = sh = 0
+        while True:
+            if i >= n or sh > 63:
+                raise ValueError("truncated proto")
+            c = raw[i]
+            i += 1
+            v |= (c & 0x7F) << sh
+            sh += 7
+            if not c & 0x80:
+                return v
+    while i < n:
+        key = varint()
+        f, wt = key >> 3, key & 7
+        if wt == 0:
+            out.append((f, wt, varint()))
+        elif wt == 2:
+            ln = varint()
+            if ln > n - i:
+                raise ValueError("truncated proto")
+            out.append((f, wt, raw[i:i + ln]))
+            i += ln
+        else:
+            raise ValueError("unsupported wire type %d" % wt)
+    return out
+
+
+def parse_signer_config(raw):
+    """IdemixSignerConfig (the proto, or the JSON form idemixgen writes) ->
+    (Credential proto, sk as 32 big-endian bytes, CredentialRevocationInformation or None)"""
+    import base64
+    import json
+    raw = bytes(raw)
+    try:
+        j = json.loads(raw)
+        cred, sk = base64.b64decode(j["Cred"]), base64.b64decode(j["Sk"])
+        cri = base64.b64decode(j.get("credential_revocation_information", ""))
+    except (ValueError, UnicodeDecodeError):
+        f = {k: v for k, wt, v in _pb_top_fields(raw) if wt == 2}
+        cred, sk, cri = f.get(1, b""), f.get(2, b""), f.get(6, b"")
+    if len(sk) > 32:
+        raise ValueError("user secret wider than 32 bytes")
+    return cred, sk.rjust(32, b"\0"), (cri or None)
+
+
+class GeneratedIdentities:
+    """what Credential.generate returns: ids (serialized identities, b"" for a rejected item),
+    rnym / r_eid / r_rh (32 big-endian bytes each) and the int32 status array"""
+
+    def __init__(self, ids, rnym, r_eid, r_rh, status):
+        self.ids, self.rnym, self.r_eid, self.r_rh, self.status = ids, rnym, r_eid, r_rh, status
+
+    def __len__(self):
+        return len(self.ids)
+
+
+class Credential:
+    """One wallet's idemix credential on the device (fts_idemix_cred): generate(n) yields what
+    n calls of KeyManager.Identity do (services/identity/idemix/km.go:173-290) -- fresh owner
+    identities with their association proof, the nym randomness for NymSigner and the audit
+    randoms.  Borrows `verifier` (an IdentityVerifier under the credential's issuer key),
+    which must stay open while this handle lives."""
+
+    def __init__(self, verifier, cred, sk, cri=None):
+        """cred: the Credential proto; sk: int or 32 big-endian bytes; cri: the
+        CredentialRevocationInformation proto or None (epoch 0, the G2 generator)"""
+        self.verifier = verifier
+        self.curve = verifier.curve
+        sk = sk.to_bytes(32, "big") if isinstance(sk, int) else bytes(sk)
+        if len(sk) != 32:
+            raise ValueError("the user secret is an int or 32 big-endian bytes")
+        cred = bytes(cred)
+        cri = None if cri is None else bytes(cri)
+        h = C.c_void_p()
+        L.check("fts_idemix_cred_create",
+                L.lib.fts_idemix_cred_create(verifier.h, cred, len(cred), sk, cri, len(cri or b""), C.byref(h)))
+        self.h = h
+
+    @classmethod
+    def from_signer_config(cls, verifier, raw, with_cri=True):
+        cred, sk, cri = parse_signer_config(raw)
+        return cls(verifier, cred, sk, cri if with_cri else None)
+
+    def close(self):
+        if getattr(self, "h", None):
+            L.lib.fts_idemix_cred_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def identity_len(self):
+        return int(L.lib.fts_idemix_identity_len(self.h))
+
+    def generate(self, n, seed=None, r_eid=None, r_rh=None, id_stride=None):
+        """n identities in one device pass -> GeneratedIdentities.  seed None: the secure
+        source, else test-only (item i equals the one-item call at seed + i).  r_eid / r_rh:
+        n ints or 32-byte strings (or one, repeated) that fix the audit randoms."""
+        ln = self.identity_len
+        stride = ln if id_stride is None else int(id_stride)
+        st = np.zeros(n, dtype=np.int32)
+
+        def fixed(v):
+            if v is None:
+                return None, None
+            vs = list(v) if isinstance(v, (list, tuple)) else [v] * n
+            if len(vs) != n:
+                raise ValueError("a fixed audit random per identity")
+            b = b"".join((x.to_bytes(32, "big") if 0 <= x < (1 << 256) else b"\xff" * 32) if isinstance(x, int)
+                         else bytes(x) for x in vs)
+            if len(b) != 32 * n:
+                raise ValueError("an audit random is an int or 32 big-endian bytes")
+            a = np.frombuffer(b, dtype=np.uint8)
+            return a, a.ctypes.data
+        keep_e, p_e = fixed(r_eid)
+        keep_r, p_r = fixed(r_rh)
+        ids = np.zeros(max(1, n * stride), dtype=np.uint8)
+        lens = np.zeros(max(1, n), dtype=np.uint32)
+        rn, re_, rr = (np.zeros(max(1, 32 * n), dtype=np.uint8) for _ in range(3))
+        sd = OS_RANDOM if seed is None else int(seed) & ((1 << 64) - 1)
+        L.check("fts_idemix_identity_generate_batch",
+                L.lib.fts_idemix_identity_generate_batch(self.h, n, sd, p_e, p_r, ids.ctypes.data, stride,
+                                                         lens.ctypes.data, rn.ctypes.data, re_.ctypes.data,
+                                                         rr.ctypes.data, st.ctypes.data_as(C.POINTER(C.c_int32))))
+        raw = ids.tobytes()
+        cut = lambda a: [a[32 * i:32 * i + 32].tobytes() for i in range(n)]  # noqa: E731
+        return GeneratedIdentities([raw[i * stride:i * stride + int(lens[i])] for i in range(n)],
+                                   cut(rn), cut(re_), cut(rr), st)
+
+    def draws(self, seed, i):
+        """the 18 scalars of item i at `seed` (fts_debug_idemix_identity_draws), as ints:
+        rnym, r1, r2, nonce, rSk, rE, rR2, rR3, rS', rRNym, rAttrs[0..3], r_eid, r_rh, rr_eid, rr_rh"""
+        return identity_draws(self.curve, seed, i)
+
+    def last_timings(self):
+        """(k_idg_prep + k_idg_points ms, k_idg_finish ms, host draw + staging s, host serialisation s)"""
+        ms, hs = (C.c_float * 2)(), (C.c_double * 2)()
+        L.check("fts_idemix_identity_generate_last_timings",
+                L.lib.fts_idemix_identity_generate_last_timings(self.h, ms, hs))
+        return float(ms[0]), float(ms[1]), float(hs[0]), float(hs[1])
+
+
+def identity_draws(curve, seed, i):
+    """host-only: the draws of Credential.generate's item i at `seed` on `curve`"""
+    out = (C.c_uint8 * (18 * 32))()
+    L.check("fts_debug_idemix_identity_draws",
+            L.lib.fts_debug_idemix_identity_draws(int(curve), int(seed), int(i), out))
+    b = bytes(out)
+    return [int.from_bytes(b[32 * k:32 * k + 32], "big") for k in range(18)]
+
+
+def write_identity(curve, points, scalars, nonce, epoch_pk=None, epoch=0):
+    """host-only: the identity writer on given values (fts_debug_idemix_identity_write).
+    points: A' ABar B' Nym EidNym RhNym as (x, y); scalars: c sSk sE sR2 sR3 sS' sAttrs[0..3]
+    sRNym sEid sRh; epoch_pk: 128 raw bytes in the curve's ECP2 order, None: the generator"""
+    pts = b"".join(x.to_bytes(32, "big") + y.to_bytes(32, "big") for x, y in points)
+    sc = b"".join(s.to_bytes(32, "big") for s in scalars)
+    if len(pts) != 384 or len(sc) != 416:
+        raise ValueError("six points and thirteen scalars")
+    n = C.c_size_t()
+    buf = (C.c_uint8 * 2048)()
+    L.check("fts_debug_idemix_identity_write",
+            L.lib.fts_debug_idemix_identity_write(int(curve), pts, sc, nonce.to_bytes(32, "big"), epoch_pk, int(epoch),
+                                                  buf, 2048, C.byref(n)))
+    return bytes(buf[:n.value])
 
 
 class AuditMatchError(Exception):

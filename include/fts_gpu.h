@@ -711,6 +711,75 @@ int fts_idemix_audit_match_batch(fts_idemix_idv* idv, size_t n, const fts_idemix
 /* HIP-event duration (ms) of the last batch's kernel (k_idv_audit). */
 int fts_idemix_audit_last_timings(fts_idemix_idv* idv, float* ms);
 
+/* ---- idemix owner identities generated on the device ----
+ * Per identity what KeyManager.Identity produces (services/identity/idemix/km.go:173-290):
+ * a fresh nym, Csp.Sign with IdemixSignerOpts{4 hidden attributes, RhIndex 3, EidIndex 2,
+ * SigType EidNymRhNym} (IBM/idemix NewSignature, no message) and the randomness of the audit
+ * info, serialized as SerializedIdemixIdentity{1 nym_public_key, 4 proof} -- what
+ * SigningIdentity.Serialize yields and fts_idemix_identity_verify_batch /
+ * fts_idemix_audit_match_batch take.
+ *
+ * One handle per credential.  cred: the idemix Credential proto (IdemixSignerConfig.Cred: A, B,
+ * E, S, attributes); sk32: the user secret, 32 B big-endian; cri: the
+ * CredentialRevocationInformation proto, or NULL (cri_len 0) for epoch 0 and the curve's G2
+ * generator as epoch_pk, as ALG_NO_REVOCATION writes it.  The handle BORROWS idv -- its device,
+ * its seven fixed-base tables and ipk.Hash -- so idv must outlive it.  It holds fixed-base
+ * tables of A and B (BN254: 2 x 32 MiB; FP256BN_AMCL: 2 x 64 MiB) and the constant points
+ * HSk sk, HAttrs[2] attrs[2], HAttrs[3] attrs[3].
+ * Checked at creation (FTS_API_EPP): exactly four attributes; A and B on the curve, A != O;
+ * sk, E, S and the attributes below r; B = g1 + HRand S + HSk sk + sum HAttrs[i] attrs[i]
+ * (Credential.Ver's B check); a CRI that does not parse, lacks its epoch key or names a
+ * revocation algorithm other than ALG_NO_REVOCATION.  FTS_API_EINVAL for a NULL argument.
+ * NOT checked: the credential's pairing equation e(W + g2 E, A) = e(g2, B), which needs a
+ * scalar product in G2 -- a forged A only yields identities that the verifier rejects.
+ * Secrets the handle holds on the device are zeroed before they are freed, on destroy and on
+ * every error path of create.  Not hardened against timing or cache side channels (table
+ * indices and branches depend on secrets), as the other signers. */
+typedef struct fts_idemix_cred fts_idemix_cred;
+int fts_idemix_cred_create(fts_idemix_idv* idv, const uint8_t* cred, size_t cred_len, const uint8_t* sk32,
+                           const uint8_t* cri, size_t cri_len, fts_idemix_cred** out);
+void fts_idemix_cred_destroy(fts_idemix_cred* c);
+/* Exact length of every identity the handle writes: a function of the curve and the CRI's epoch
+ * (BN254 1113 bytes, FP256BN_AMCL 1114, at epoch 0). */
+size_t fts_idemix_identity_len(const fts_idemix_cred* c);
+/* n identities.  Identity i is written at ids + i * id_stride, id_len[i] <- its length;
+ * rnym32 <- the nym's randomness (what fts_nym_sign_batch takes), r_eid32 / r_rh32 <-
+ * EidNymAuditData.Rand / RhNymAuditData.Rand of the audit info (n x 32 B big-endian each).
+ * r_eid_in32 / r_rh_in32 (n x 32 B each, or NULL): the Identity(auditInfo) case of
+ * km.go:199-209, the caller fixes the audit randoms so that EidNym / RhNym equal an earlier
+ * identity's.  An in-value >= r gives status[i] = FTS_E_SIGN_BADKEY, zero outputs
+ * (id_len[i] = 0) and leaves the other items alone; every other status is FTS_OK.
+ * Randomness: item i draws from RngSource(seed).at(i) on the host (seeded: the stream of
+ * seed + i, tests only; FTS_SEED_OS_RANDOM: the secure source), uniform below r by rejection,
+ * in this order:
+ *   rnym, r1, r2, nonce, rSk, rE, rR2, rR3, rS', rRNym, rAttrs[0..3], r_eid, r_rh, rr_eid, rr_rh
+ * (rnym, then the order of IBM/idemix NewSignature as oracle/idemix_identity.py sign restates
+ * it); r1 = 0 is redrawn; with r_*_in32 the drawn value is consumed, then replaced.
+ * FTS_API_ESIZE, before a byte is written, if id_stride < fts_idemix_identity_len; n = 0 is
+ * FTS_API_OK; FTS_API_EINVAL for a NULL handle or output array or n > 2^22; FTS_API_EDEVICE
+ * for a device failure or a failure of the OS random source (getrandom), as the other
+ * signers.  Thread-safe: up to 3 calls on one handle run concurrently (a slot each; the staged
+ * draws are wiped from the slot on every way out).  A call above 16,384 identities runs in
+ * tiles of that size, so a slot holds at most 72 MB of device memory.
+ * The device hands back six points and thirteen scalars per identity (c and the twelve
+ * responses); the nonce is written from the host's draws. */
+int fts_idemix_identity_generate_batch(fts_idemix_cred* c, size_t n, uint64_t seed, const uint8_t* r_eid_in32,
+                                       const uint8_t* r_rh_in32, uint8_t* ids, size_t id_stride, uint32_t* id_len,
+                                       uint8_t* rnym32, uint8_t* r_eid32, uint8_t* r_rh32, int32_t* status);
+/* The last finished call: ms2[0] = k_idg_prep + k_idg_points, ms2[1] = k_idg_finish (HIP events);
+ * host_s2 (may be NULL): seconds of the host pool drawing + staging, and serialising. */
+int fts_idemix_identity_generate_last_timings(fts_idemix_cred* c, float* ms2, double* host_s2);
+/* Host-only (tests): the 18 scalars above of item i at `seed` (not FTS_SEED_OS_RANDOM),
+ * 18 x 32 B big-endian.  r1 cannot be recovered from A', so a byte-exact comparison with the
+ * oracle's signer needs them. */
+int fts_debug_idemix_identity_draws(int curve_id, uint64_t seed, uint64_t i, uint8_t* out18x32);
+/* Host-only (tests): the identity writer on given values.  pts6x64: A' ABar B' Nym EidNym RhNym
+ * (X || Y); sc13x32: c sSk sE sR2 sR3 sS' sAttrs[0..3] sRNym sEid sRh; epoch_pk128 NULL: the
+ * generator.  *out_len <- the length; FTS_API_ESIZE (nothing written) if out_cap is below it. */
+int fts_debug_idemix_identity_write(int curve_id, const uint8_t* pts6x64, const uint8_t* sc13x32,
+                                    const uint8_t* nonce32, const uint8_t* epoch_pk128, uint64_t epoch, uint8_t* out,
+                                    size_t out_cap, size_t* out_len);
+
 #ifdef __cplusplus
 }
 #endif
