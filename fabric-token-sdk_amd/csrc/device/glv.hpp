@@ -386,11 +386,11 @@ FTS_DEV G1J straus2_atab(const ATab& T, const uint32_t a[4], const uint32_t b[4]
 }
 
 // ------------------------------------------- per-proof shared tables (com chain)
-// k_rp_com_var's two lanes of a proof share ONE affine table: lane 0 builds and
-// normalises 1..8 D (entries 0..7), lane 1 1..8 S (entries 8..15), unsigned and
-// without phi; each entry also carries beta*x, so the lane of the phi half reads
-// phi(e P) = (beta x, y) and applies its GLV sign to y at lookup.  Half the table
-// work and one inversion per lane of the per-lane tables (ATab).
+// One affine table per proof: k_rp_com_tab builds and normalises 1..8 D (entries
+// 0..7) in one lane and 1..8 S (entries 8..15) in another, unsigned and without phi;
+// each entry also carries beta*x, so the chain (k_rp_com_var, one lane per proof,
+// straus4_ctab) reads phi(e P) = (beta x, y) for the phi halves and applies the GLV
+// signs to y at lookup.
 // Region layout: XY [16][B][16] | BX [16][B][8] | Z [16][B][8] | PRE [16][B][8]
 // (2,560 B per proof), row (e, proof) entry-major.
 constexpr int CTAB_WORDS = 16 * 40;  // words per proof
@@ -461,35 +461,76 @@ FTS_DEV void ctab_build8(const TabT& T, int e0, const G1J& P, bool ident) {
     store_fp(T.bx(e0 + e), fp_mul(x, beta));
   }
 }
-// a phi^h(sa D) + b phi^h(sb S) over the shared table (sa, sb: the GLV signs of the
-// two half scalars, folded into y at lookup): 124 doublings, <= 64 mixed additions
-FTS_DEV G1J straus2_ctab(const CTab& T, int h, const uint32_t a[4], bool sa, const uint32_t b[4], bool sb, bool ida,
-                         bool idb) {
-  const uint32_t ca = recode_carries(a), cb = recode_carries(b);
+// a1 (s1 D) + a2 phi(s2 D) + b1 (t1 S) + b2 phi(t2 S) over the proof's table, in ONE
+// accumulator (s1, s2, t1, t2: the GLV signs of the four half scalars, folded into y
+// at lookup): 124 doublings and <= 128 mixed additions, where a chain per phi half
+// doubles 2 x 124 times.  Step j = 4 (31 - w) + i adds term i of window w (MSB
+// first): i & 2 picks S's rows (8..15) over D's, i & 1 the beta*x column (phi) over
+// x.  One madd_inl body serves all four terms (four inlined copies would not fit the
+// instruction cache beside the doublings); the step's scalar, carries
+// and sign are chosen by selects on values (no runtime-indexed arrays).  The row
+// of step j + 1 is loaded before step j's addition -- for i = 3 also before the next
+// window's four doublings -- so its latency hides behind them; y is negated only at
+// the addition, so nothing waits for the load earlier.  idD / idS: D / S is the
+// identity (its rows are (0, 0) and its terms are skipped).
+// The four half scalars are copied into plain words first: a select between loads
+// through two pointers becomes a load through a selected pointer, which again puts
+// the arrays into LDS.
+struct Straus4 {
+  uint32_t a1[4], a2[4], b1[4], b2[4];
+  uint32_t c0, c1, c2, c3;  // recode_carries of a1, a2, b1, b2
+  bool s1, s2, t1, t2, idD, idS;
+};
+FTS_DEV G1J straus4_ctab(const CTab& T, const uint32_t a1[4], bool s1, const uint32_t a2[4], bool s2,
+                         const uint32_t b1[4], bool t1, const uint32_t b2[4], bool t2, bool idD, bool idS) {
+  Straus4 K;
+#pragma unroll
+  for (int l = 0; l < 4; l++) K.a1[l] = a1[l], K.a2[l] = a2[l], K.b1[l] = b1[l], K.b2[l] = b2[l];
+  K.c0 = recode_carries(a1), K.c1 = recode_carries(a2), K.c2 = recode_carries(b1), K.c3 = recode_carries(b2);
+  K.s1 = s1, K.s2 = s2, K.t1 = t1, K.t2 = t2, K.idD = idD, K.idS = idS;
   G1J acc = g1j_identity();
-  for (int w = 31; w >= 0; w--) {
-    const int da = ida ? 0 : window_digit(a, ca, w), db = idb ? 0 : window_digit(b, cb, w);
-    G1A qa, qb;
-    if (da != 0) {
-      const int e = (da < 0 ? -da : da) - 1;
-      load_fp(h ? T.bx(e) : T.xy(e), qa.x);
-      load_fp(T.xy(e) + 8, qa.y);
+  G1A q;
+  int d = 0;  // step j's signed digit with the term's GLV sign folded in; 0: nothing to add
+  // j = -1 only loads step 0's row (one copy of the lookup in the code)
+#pragma unroll 1
+  for (int j = -1; j < 128; j++) {
+    G1A qn;  // zero unless step j + 1 has a row to add
+    qn.x = f_zero<FpP>();
+    qn.y = f_zero<FpP>();
+    int dn = 0;
+    {
+      const int jn = j + 1, w = 31 - (jn >> 2), i = jn & 3;
+      const bool hi = (i & 2) != 0, ph = (i & 1) != 0;
+      // the term's scalar word by word, then the window's word (window_digit on values)
+      const uint32_t w0 = hi ? (ph ? K.b2[0] : K.b1[0]) : (ph ? K.a2[0] : K.a1[0]);
+      const uint32_t w1 = hi ? (ph ? K.b2[1] : K.b1[1]) : (ph ? K.a2[1] : K.a1[1]);
+      const uint32_t w2 = hi ? (ph ? K.b2[2] : K.b1[2]) : (ph ? K.a2[2] : K.a1[2]);
+      const uint32_t w3 = hi ? (ph ? K.b2[3] : K.b1[3]) : (ph ? K.a2[3] : K.a1[3]);
+      const uint32_t word = (w & 16) ? ((w & 8) ? w3 : w2) : ((w & 8) ? w1 : w0);
+      const uint32_t cm = hi ? (ph ? K.c3 : K.c2) : (ph ? K.c1 : K.c0);
+      const bool sg = hi ? (ph ? K.t2 : K.t1) : (ph ? K.s2 : K.s1);
+      int dw = 0;
+      if (jn < 128 && !(hi ? K.idS : K.idD)) {
+        const int raw = (int)((word >> (4 * (w & 7))) & 0xfu), cin = (int)((cm >> w) & 1u);
+        const int cout = w < 31 ? (int)((cm >> (w + 1)) & 1u) : 0;
+        dw = raw + cin - 16 * cout;
+      }
+      if (dw != 0) {
+        const int ad = dw < 0 ? -dw : dw, e = (hi ? 8 : 0) + ad - 1;
+        const uint32_t* px = ph ? T.bx(e) : T.xy(e);
+        load_fp(px, qn.x);
+        load_fp(T.xy(e) + 8, qn.y);
+        dn = ((dw < 0) != sg) ? -ad : ad;
+      }
     }
-    if (db != 0) {
-      const int e = 8 + (db < 0 ? -db : db) - 1;
-      load_fp(h ? T.bx(e) : T.xy(e), qb.x);
-      load_fp(T.xy(e) + 8, qb.y);
-    }
-    if (w != 31)
+    if (j > 0 && (j & 3) == 0)
       for (int r = 0; r < 4; r++) acc = g1j_dbl(acc);
-    if (da != 0) {
-      if ((da < 0) != sa) qa.y = f_neg(qa.y);
-      madd_inl(acc, qa);
+    if (d != 0) {
+      if (d < 0) q.y = f_neg(q.y);
+      madd_inl(acc, q);
     }
-    if (db != 0) {
-      if ((db < 0) != sb) qb.y = f_neg(qb.y);
-      madd_inl(acc, qb);
-    }
+    d = dn;
+    q = qn;
   }
   return acc;
 }

@@ -19,9 +19,9 @@ constexpr int NORM_E = 16;  // nominal, for the cost model
 constexpr size_t NORM_BIG = (size_t)1 << 16;
 // k_rp_powers: indices per lane (the chunk's low bits expand as a binary tree)
 constexpr int PW_LC = 3, PW_CH = 1 << PW_LC;
-// com terms per proof, work path (com_terms): 0 z*K, 1 -delta*P, 2,3 the GLV halves of x*D,
-// 4,5 the GLV halves of z^2*S.
-constexpr int COM_NTERMS = 4;  // z K, -delta P, the two joint GLV halves
+// com terms per proof, work path: slots 0 z*K, 1 -delta*P (k_rp_fixed_exact ->
+// k_rp_com_var)
+constexpr int COM_NTERMS = 2;
 // Horner chunks of S = sum_i 2^i H'_i: 16 H' per chunk (4 chunks at n = 64),
 // joined once per proof by k_rp_hsum_join (slot 0 of the proof's chunks)
 constexpr int HS_CHUNK = 16;
@@ -54,6 +54,8 @@ __global__ void k_rp_fixed_exact(int B, int n, int k, const int32_t* status, con
                                  const uint32_t* ypow, const uint32_t* wtables, uint32_t* hpj, uint32_t* terms);
 __global__ void k_rp_hsum_chunks(int B, int n, const int32_t* status, const uint32_t* hpj, uint32_t* chunks);
 __global__ void k_rp_hsum_join(int B, int n, const int32_t* status, uint32_t* chunks);
+__global__ void k_rp_com_tab(int B, int n, int k, const int32_t* status, const uint32_t* pts, const uint32_t* chunks,
+                             uint32_t* atab);
 __global__ void k_rp_com_var(int B, int n, int k, const int32_t* status, const uint32_t* pts, const uint32_t* ch,
                              const uint32_t* chunks, uint32_t* atab, const uint32_t* terms, uint32_t* hpj,
                              uint32_t* hpa, uint8_t* hp_be);

@@ -308,10 +308,37 @@ __global__ void __launch_bounds__(256) k_rp_hsum_join(int B, int n, const int32_
   store_g1j(Sc, S);
 }
 
-// x*D + z^2*S (bulletproof.go:478, 486-489 via S), two lanes per proof: with
-// x = x1 + x2 lambda and z^2 = w1 + w2 lambda (GLV), lane h computes
-// x_h phi^h(D) + w_h phi^h(S) in one joint Straus chain over an affine lane
-// table (glv.hpp straus2_atab); S from k_rp_hsum_join -> terms[b][2 + h]
+// The affine tables of the com chain (glv.hpp CTab), one per proof: 1..8 D in rows
+// 0..7, 1..8 S (S from k_rp_hsum_join) in rows 8..15, each normalised with one
+// inversion.  The first half of the grid's blocks builds D's rows (D is affine: a
+// mixed doubling and mixed additions), the second half S's (full additions), so every
+// wave runs one instruction stream; the chain reads the rows after the launch
+// boundary (no fence, no barrier).  Launched with 2 * ceil(B / blockDim.x) blocks
+__global__ void __launch_bounds__(256) k_rp_com_tab(int B, int n, int k, const int32_t* __restrict__ status,
+                                                   const uint32_t* __restrict__ pts,
+                                                   const uint32_t* __restrict__ chunks, uint32_t* __restrict__ atab) {
+  wave_prio<PS_COMVAR>();
+  const int nb = gridDim.x >> 1;
+  const bool h = (int)blockIdx.x >= nb;
+  const int b = ((int)blockIdx.x - (h ? nb : 0)) * blockDim.x + threadIdx.x;
+  if (b >= B || status[b] != 0) return;
+  const CTab T{atab, (size_t)B, (size_t)b};
+  if (!h) {
+    const G1A Da = load_g1a(pts + ((size_t)b * rp_npts(k) + RP_PT_D) * 16);
+    ctab_build8<true>(T, 0, g1j_from_affine(Da), g1a_is_identity(Da));
+  } else {
+    const int nc = (n + HS_CHUNK - 1) / HS_CHUNK;
+    const G1J S = load_g1j(chunks + (size_t)b * nc * 24);
+    ctab_build8<false>(T, 8, S, f_is_zero(S.z));
+  }
+}
+
+// com = C + z K - delta P + x D + z^2 S (bulletproof.go:477-492), one lane per
+// proof: with x = x1 + x2 lambda and z^2 = w1 + w2 lambda (GLV), x D + z^2 S =
+// x1 D + x2 phi(D) + w1 S + w2 phi(S) is ONE joint Straus chain over the proof's
+// table (glv.hpp straus4_ctab; k_rp_com_tab built it), 124 doublings where a lane
+// per phi half doubled 2 x 124 times; then the fixed-base terms z K, -delta P
+// (k_rp_fixed_exact -> terms[b][0..1]) and C, and com's own normalisation
 #ifndef FTS_COMVAR_OCC
 #define FTS_COMVAR_OCC 3  // waves per SIMD the register budget allows (A/B builds: -DFTS_COMVAR_OCC=4)
 #endif
@@ -321,62 +348,35 @@ __global__ void __launch_bounds__(256, FTS_COMVAR_OCC) k_rp_com_var(int B, int n
                                                    const uint32_t* __restrict__ terms, uint32_t* __restrict__ hpj,
                                                    uint32_t* __restrict__ hpa, uint8_t* __restrict__ hp_be) {
   wave_prio<PS_COMVAR>();
-  const int gid = blockIdx.x * blockDim.x + threadIdx.x;
-  const int b = gid >> 1, h = gid & 1;
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= B || status[b] != 0) return;
   const uint32_t* C = ch + (size_t)b * rp_nch(k) * 8;
   Fr x, z2;
   load_f(C + CH_X * 8, x);
   load_f(C + CH_Z2 * 8, z2);
-  // this lane's GLV halves by selects, not by indexing [h]: a runtime index made
-  // the compiler keep the arrays in LDS (16 KB per 64-lane block), and com_var's
-  // blocks then held every CU's LDS and starved the x0 build beside them (round 5)
-  uint32_t xa[4], xb[4], xs0, xs1, wa[4], wb[4], ws0, ws1, xh[4], wh[4];
+  uint32_t xa[4], xb[4], xs0, xs1, wa[4], wb[4], ws0, ws1;
   glv_decompose(fr_canon(x).v, xa, xs0, xb, xs1);
   glv_decompose(fr_canon(z2).v, wa, ws0, wb, ws1);
-#pragma unroll
-  for (int q = 0; q < 4; q++) {
-    xh[q] = h ? xb[q] : xa[q];
-    wh[q] = h ? wb[q] : wa[q];
-  }
-  const bool xsh = (h ? xs1 : xs0) != 0, wsh = (h ? ws1 : ws0) != 0;
   const int nc = (n + HS_CHUNK - 1) / HS_CHUNK;
-  G1J S = load_g1j(chunks + (size_t)b * nc * 24);  // k_rp_hsum_join
-  const G1A Da = load_g1a(pts + ((size_t)b * rp_npts(k) + RP_PT_D) * 16);
-  const bool idD = g1a_is_identity(Da), idS = f_is_zero(S.z);
-  // the proof's shared table: lane 0 builds 1..8 D, lane 1 1..8 S (one instruction
-  // stream on the lane's own point: no divergence).  Both lanes of a proof are
-  // adjacent lanes (gid 2b, 2b + 1) of ONE wave64 wave, which runs them in
-  // lockstep: the fence makes each lane's row stores visible, the wave barrier
-  // keeps the compiler from moving the other lane's reads above it
-  static_assert(256 % 64 == 0, "k_rp_com_var: a proof's lane pair must sit in one wave");
+  // the identity flags as k_rp_com_tab saw them: S's z (k_rp_hsum_join), D's coordinates
+  Fp sz;
+  load_fp(chunks + (size_t)b * nc * 24 + 16, sz);
+  const bool idS = f_is_zero(sz);
+  const bool idD = g1a_is_identity(load_g1a(pts + ((size_t)b * rp_npts(k) + RP_PT_D) * 16));
   const CTab T{atab, (size_t)B, (size_t)b};
-  const G1J Dj = g1j_from_affine(Da);
-  ctab_build8<false>(T, 8 * h, h ? S : Dj, h ? idS : idD);
-  __threadfence_block();
-  __builtin_amdgcn_wave_barrier();
-  G1J r = straus2_ctab(T, h, xh, xsh, wh, wsh, idD, idS);
-  // com = C + z K - delta P + x D + z^2 S (bulletproof.go:477-492), summed by the
-  // proof's two lanes (adjacent lanes of one wave; both exit or both run): lane h
-  // adds its fixed-base term (z K or -delta P, k_rp_fixed_exact), lane 0 also C,
-  // then lane 0 adds lane 1's partial (cross-lane shuffle) and writes com
-  add_inl(r, load_g1j(terms + ((size_t)b * COM_NTERMS + h) * 24));
-  G1J c = g1j_identity();
-  if (h == 0) c = g1j_from_affine(load_g1a(pts + ((size_t)b * rp_npts(k) + RP_PT_C) * 16));
-  add_inl(r, c);
-  G1J o;
-#pragma unroll
-  for (int q = 0; q < 8; q++) {
-    o.x.v[q] = __shfl_xor(r.x.v[q], 1);
-    o.y.v[q] = __shfl_xor(r.y.v[q], 1);
-    o.z.v[q] = __shfl_xor(r.z.v[q], 1);
+  G1J r = straus4_ctab(T, xa, xs0 != 0, xb, xs1 != 0, wa, ws0 != 0, wb, ws1 != 0, idD, idS);
+  // + z K - delta P + C: three full additions through ONE add_inl body (a second
+  // madd_inl copy for the affine C would cost more code than its 5 products save)
+#pragma unroll 1
+  for (int h = 0; h < 3; h++) {
+    G1J t;
+    if (h < 2) t = load_g1j(terms + ((size_t)b * COM_NTERMS + h) * 24);
+    else t = g1j_from_affine(load_g1a(pts + ((size_t)b * rp_npts(k) + RP_PT_C) * 16));
+    add_inl(r, t);
   }
-  if (h == 0) {
-    add_inl(r, o);
-    const size_t q = (size_t)b * (n + 1) + n;
-    store_g1j(hpj + q * 24, r);
-    store_affine_one(r, hpa + q * 16, hp_be + q * 64);  // com for the x0 suffix (no normalize_com launch)
-  }
+  const size_t q = (size_t)b * (n + 1) + n;
+  store_g1j(hpj + q * 24, r);
+  store_affine_one(r, hpa + q * 16, hp_be + q * 64);  // com for the x0 suffix (no normalize_com launch)
 }
 
 // ----------------------------------------- com, latency path (small passes)

@@ -16,7 +16,8 @@
 //   S   k_rp_normalize     point (block)    batch affine normalisation of H'_i (one inversion per block)
 //   S   k_rp_hsum_chunks   (proof, chunk)   S_c = sum_j 2^j H'_{16c+j} (Horner)
 //   S   k_rp_hsum_join     proof            S = sum_c 2^(16c) S_c
-//   S   k_rp_com_var       2 lanes/proof    x*D + z^2*S (joint GLV/Straus, affine lane tables),
+//   S   k_rp_com_tab       2 lanes/proof    affine tables 1..8 D and 1..8 S with beta*x (one inversion each)
+//   S   k_rp_com_var       proof            x*D + z^2*S (ONE joint GLV/Straus chain over the proof's table),
 //                                           com = C + z K - delta P + x D + z^2 S       bulletproof.go:477-492
 //   S2  k_rp_x0_build/hash proof            x0 prefix: H' records + shared template     ipa.go:200-213
 //   S   k_rp_x0_build/hash proof            x0 suffix after com: x0 = HashToZr(...)     ipa.go:213
@@ -253,10 +254,15 @@ void exact_work_path(const Pass& p) {
   p.tl->mark("k_rp_hsum_chunks", p.s, (double)B * (n - nch) * (COST_DBL + COST_ADD));
   FTS_LAUNCH(k_rp_hsum_join, B, g_chain_bs, p.s, B, n, d.status, d.scratch);
   p.tl->mark("k_rp_hsum_join", p.s, (double)B * (nch - 1) * (HS_CHUNK * COST_DBL + COST_ADD));
-  // scratch: [0, B*HS_SCRATCH) Horner chunks of S, then the 2B lanes' affine tables
-  FTS_LAUNCH(k_rp_com_var, 2 * B, g_chain_bs, p.s, B, n, k, d.status, d.pts, d.ch, d.scratch,
+  // scratch: [0, B*HS_SCRATCH) Horner chunks of S, then the B proofs' affine tables.
+  // k_rp_com_tab: ceil(B / bs) blocks for D's rows, then as many for S's
+  const size_t tab_blocks = ((size_t)B + g_chain_bs - 1) / g_chain_bs;
+  FTS_LAUNCH(k_rp_com_tab, 2 * tab_blocks * g_chain_bs, g_chain_bs, p.s, B, n, k, d.status, d.pts, d.scratch,
+             d.scratch + (size_t)B * HS_SCRATCH);
+  p.tl->mark("k_rp_com_tab", p.s, (double)B * (COST_CTAB8_AFF + COST_CTAB8_JAC));
+  FTS_LAUNCH(k_rp_com_var, B, g_chain_bs, p.s, B, n, k, d.status, d.pts, d.ch, d.scratch,
              d.scratch + (size_t)B * HS_SCRATCH, d.terms, d.hpj, d.hpa, d.hp_be);
-  p.tl->mark("k_rp_com_var", p.s, (double)B * (2 * (COST_STRAUS2_CTAB + 2.5 * COST_ADD) + COST_NORM1));
+  p.tl->mark("k_rp_com_var", p.s, (double)B * (COST_STRAUS4_CTAB + 3.0 * COST_ADD + COST_NORM1));
 }
 
 // x0 on s: the message (its tail only, with the prefix split) and its hash

@@ -5,6 +5,8 @@
 //   arith_check IN OUT   one record per line of IN: "op operand operand ...";
 //                        one result line per record in OUT, in input order
 //   arith_check --list   the op catalogue ("name operands results"), no device
+//   arith_check --list-chain   the same for the com chain's op (straus4_ctab:
+//                        tests/com_chain_vectors.py), kept apart from the primitives' list
 //
 // An operand or result is one 256-bit word in hex (most significant digit first):
 // the 8 little-endian uint32 limbs exactly as the device function takes and
@@ -33,7 +35,7 @@
 #define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fprintf(stderr, "%s:%d %s\n", __FILE__, __LINE__, hipGetErrorString(e_)); exit(1);} } while (0)
 
 struct Aux {  // lane tables of the scalar products (sized as in glv_check.cpp)
-  uint32_t* tab;  // [16 entries][24 words][n lanes]
+  uint32_t* tab;  // [16 entries][24 words][n lanes], or one CTab of n proofs (straus4_ctab)
   uint32_t* scr;  // 10 * 24 words per lane
   size_t n;
 };
@@ -149,6 +151,13 @@ OP(VarBaseMul, 3, 3, stj(r, fts::var_base_mul(lda(a, 0), ld<fts::Scalar>(a, 2), 
 OP(GlvMul, 3, 3, stj(r, fts::glv_mul(lda(a, 0), ld<fts::Scalar>(a, 2), x.tab, x.n, i)););
 OP(Vb128j, 4, 3, stj(r, fts::vb128j(ldj(a, 0), a + 24, x.tab, x.n, i)););
 OP(Straus2, 8, 3, stj(r, fts::straus2_128(ldj(a, 0), a + 24, ldj(a, 4), a + 56, x.tab, x.n, i)););
+// the com chain (glv.hpp).  straus4_ctab: D (affine), S (Jacobian), then
+// |a1| s1 |a2| s2 |b1| t1 |b2| t2; the lane builds its proof's CTab (D's rows as
+// k_rp_com_tab does, then S's) in the table buffer and runs the chain over it
+OP(Straus4Ctab, 13, 3, const fts::CTab T{x.tab, x.n, i}; const fts::G1A D = lda(a, 0); const fts::G1J S = ldj(a, 2);
+   const bool idD = fts::g1a_is_identity(D); const bool idS = fts::f_is_zero(S.z);
+   fts::ctab_build8<true>(T, 0, fts::g1j_from_affine(D), idD); fts::ctab_build8<false>(T, 8, S, idS);
+   stj(r, fts::straus4_ctab(T, a + 40, a[48] != 0, a + 56, a[64] != 0, a + 72, a[80] != 0, a + 88, a[96] != 0, idD, idS)););
 
 // GLV decomposition (glv.hpp): k -> |k1|, s1, |k2|, s2
 TOP(K, GlvDec, 1, 4, uint32_t k1[4]; uint32_t k2[4]; uint32_t s1; uint32_t s2; fts::glv_decompose<K>(a, k1, s1, k2, s2);
@@ -260,6 +269,7 @@ static bool chk_affine0(const uint32_t* a) {
 }
 static bool chk_jac0(const uint32_t* a) { return jac_on_curve(hfp(a), hfp(a + 8), hfp(a + 16)); }
 static bool chk_jac0_jac4(const uint32_t* a) { return chk_jac0(a) && chk_jac0(a + 32); }
+static bool chk_aff0_jac2(const uint32_t* a) { return chk_affine0(a) && chk_jac0(a + 16); }
 // cond_sub<P>(x, carry): x + carry 2^256 < 2M
 template <int MI>
 static bool chk_cond_sub(const uint32_t* a) {
@@ -375,6 +385,14 @@ static std::vector<Entry> catalogue() {
   tower<pair::FbnField>(c, "fbn", '4');
   return c;
 }
+// the com chain's op: run by name like the catalogue's, listed by --list-chain.  It has
+// a list of its own only because tests/test_arith_vectors_cpu.py compares `--list` with
+// the catalogue tests/arith_vectors.py states, op for op, and that catalogue stays as it is
+static std::vector<Entry> chain_ops() {
+  std::vector<Entry> c;
+  c.push_back(E<Straus4Ctab>("straus4_ctab", "00000mcmcmcmc", &chk_aff0_jac2, true));
+  return c;
+}
 
 // ------------------------------------------------------------------- host: io
 static bool parse_word(const char* s, uint32_t w[8]) {
@@ -399,13 +417,19 @@ struct Batch {
 };
 
 int main(int argc, char** argv) {
-  const std::vector<Entry> cat = catalogue();
+  std::vector<Entry> cat = catalogue();
+  const std::vector<Entry> chain = chain_ops();
   if (argc == 2 && !strcmp(argv[1], "--list")) {
     for (const Entry& e : cat) printf("%s %d %d\n", e.name, e.ni, e.no);
     return 0;
   }
+  if (argc == 2 && !strcmp(argv[1], "--list-chain")) {
+    for (const Entry& e : chain) printf("%s %d %d\n", e.name, e.ni, e.no);
+    return 0;
+  }
+  cat.insert(cat.end(), chain.begin(), chain.end());
   if (argc != 3) {
-    fprintf(stderr, "usage: %s IN OUT | --list\n", argv[0]);
+    fprintf(stderr, "usage: %s IN OUT | --list | --list-chain\n", argv[0]);
     return 2;
   }
   FILE* fi = fopen(argv[1], "r");
@@ -471,7 +495,7 @@ int main(int argc, char** argv) {
     CK(hipMalloc(&din, b.in.size() * 4));
     CK(hipMalloc(&dout, out_words * 4));
     if (e.aux) {
-      CK(hipMalloc(&x.tab, n * 16 * 24 * 4));
+      CK(hipMalloc(&x.tab, n * (size_t)fts::CTAB_WORDS * 4));  // >= 16 * 24 words per lane
       CK(hipMalloc(&x.scr, n * 10 * 24 * 4));
     }
     CK(hipMemcpy(din, b.in.data(), b.in.size() * 4, hipMemcpyHostToDevice));

@@ -16,7 +16,7 @@ ev = sorted((int(r["Start_Timestamp"]), int(r["End_Timestamp"]),
 fx = [e for e in ev if e[2] == "k_rp_fixed_exact"]
 fx = fx[:-R] if len(fx) > R else fx
 T0, T1 = fx[len(fx) // 8][0], fx[-1][1]  # skip the warmup's first passes
-CHAIN = {"k_rp_hsum_chunks", "k_rp_hsum_join", "k_rp_com_var", "k_rp_normalize", "k_rp_x0_hash"}
+CHAIN = {"k_rp_hsum_chunks", "k_rp_hsum_join", "k_rp_com_tab", "k_rp_com_var", "k_rp_normalize", "k_rp_x0_hash"}
 ch = [e for e in ev if e[2] in CHAIN and T0 <= e[0] < T1]
 fxs = [e for e in fx if T0 <= e[0] < T1]
 
