@@ -309,6 +309,10 @@ static int ctx_create(const uint8_t* pp_bytes, size_t pp_len, uint32_t bits, int
 // verdicts come back in caller order.  The reference verifies every action
 // independently (core/common/validator.go:215-224), so no data crosses devices;
 // each device closes its own random-linear-combination check.
+// The device provers, the commit call and the generators split the same way
+// (over_devices): the parent checks the batch and makes the call's one RngSource,
+// every child proves its slice at the items' indices in the caller's batch, and
+// the parent packs once.
 extern "C" int fts_shard_plan(size_t n, const double* weights, int nshards, size_t* bounds) {
   if (nshards < 1 || !bounds) return FTS_API_EINVAL;
   double tot = 0;
@@ -423,6 +427,23 @@ int fts_ctx_table_info(const fts_ctx* c, int shard, fts_table_info* o) {
   o->narrow_refs = DevTableCache::refs(c->d_tables.e), o->wide_refs = DevTableCache::refs(c->d_wtables.e);
   o->narrow_built = c->d_tables.built, o->wide_built = c->d_wtables.built;
   return FTS_API_OK;
+}
+
+int fts_debug_shard_work(const fts_ctx* c, int shard, int64_t out[4]) {
+  if (!c || !out) return FTS_API_EINVAL;
+  if (!c->shards.empty()) {
+    if (shard < 0 || shard >= (int)c->shards.size()) return FTS_API_EINVAL;
+    return fts_debug_shard_work(c->shards[shard], 0, out);
+  }
+  if (shard != 0 || c->device < 0) return FTS_API_EINVAL;  // host-only: no device work to count
+  out[0] = c->st_pv_proofs, out[1] = c->st_pv_actions, out[2] = c->st_pv_tokens, out[3] = c->st_pv_passes;
+  return FTS_API_OK;
+}
+
+int fts_debug_shard_timings(const fts_ctx* c, int shard, const char** names, float* ms, int cap) {
+  if (!c || shard < 0) return 0;
+  if (c->shards.empty()) return shard == 0 ? fts_last_timings_ex(c, names, ms, nullptr, cap) : 0;
+  return shard < (int)c->shards.size() ? fts_last_timings_ex(c->shards[shard], names, ms, nullptr, cap) : 0;
 }
 
 int fts_table_cache_stats(int device, struct fts_table_cache_stats* o) {

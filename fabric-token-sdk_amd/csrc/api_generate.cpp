@@ -70,6 +70,7 @@ int token_commit_device(fts_ctx* c, size_t n, const CommitItem& item, uint8_t* c
     L.tl.begin(L.s);
     HIP_OK(hipMemcpyAsync(d, h_sc, B * 96, hipMemcpyHostToDevice, L.s));
     L.tl.mark("h2d_commit", L.s, 0);
+    c->st_pv_tokens += (int64_t)B, c->st_pv_passes++;
     launch_token_commit((int)B, commit_per_lane(), reinterpret_cast<const uint32_t*>(d), c->d_tables.as<uint32_t>(),
                         c->n, reinterpret_cast<uint32_t*>(d + B0 * 160), reinterpret_cast<uint32_t*>(d + B0 * 192),
                         d + B0 * 96, L.s);
@@ -99,10 +100,49 @@ int generate_host(const fts_ctx* c, const fts_gen_action* a, bool issue, uint64_
   return gen_host_one(T, c->pp, c->n, c->k, *a, issue, src.at(0), src.at(GEN_BF_STREAM), *out);
 }
 
+// Steps 1-3 of generation for actions [lo, hi) of a call on one device context: action i
+// (its index in the caller's batch) draws its blinding factors from src.at(GEN_BF_STREAM + i)
+// and its prover scalars from src.at(i), whichever device it runs on.  Blinding factors and
+// commitments go into the caller's arrays at the outputs' offsets in the call (first[i]),
+// proofs[i] <- the action's proof.
+int generate_slice(fts_ctx* c, size_t lo, size_t hi, const fts_gen_action* acts, bool issue, const RngSource& src,
+                   const std::vector<size_t>& first, const std::vector<size_t>& in_first, fts_gen_result* out,
+                   std::string* proofs) {
+  const size_t A = hi - lo, t0 = first[lo], T = first[hi] - t0, q0 = in_first[lo], Q = in_first[hi] - q0;
+  // 1. blinding factors (into the caller's array) and the provers' witnesses
+  std::vector<uint64_t> ov(T), iv(Q);
+  std::vector<uint8_t> ib(32 * Q);
+  std::vector<uint32_t> owner_of(T);
+  std::vector<fts_action_witness> w(A);
+  parallel_for(A, 256, [&](size_t s) {
+    const size_t i = lo + s, f = first[i] - t0, fi = in_first[i] - q0;
+    const fts_gen_action& a = acts[i];
+    gen_draw_bfs(src.at(GEN_BF_STREAM + i), a.n_out, out->bf32 + 32 * first[i]);
+    for (size_t j = 0; j < a.n_out; j++) ov[f + j] = a.outputs[j].value, owner_of[f + j] = (uint32_t)i;
+    const size_t nin = issue ? 0 : a.n_in;
+    for (size_t q = 0; q < nin; q++) {
+      iv[fi + q] = a.inputs[q].value;
+      memcpy(ib.data() + 32 * (fi + q), a.inputs[q].bf32, 32);
+    }
+    w[s] = fts_action_witness{a.type, a.type_len, nin, iv.data() + fi, ib.data() + 32 * fi,
+                              a.n_out, ov.data() + f, out->bf32 + 32 * first[i]};
+  });
+  // 2. the outputs' commitments (into the caller's array)
+  int rc = token_commit_device(c, T, [&](size_t t, const uint8_t*& type, size_t& type_len, uint64_t& value,
+                                         const uint8_t*& bf32) {
+    const fts_gen_action& a = acts[owner_of[t]];
+    type = a.type, type_len = a.type_len, value = ov[t], bf32 = out->bf32 + 32 * (t0 + t);
+  }, out->com64 + 64 * t0);
+  if (rc) return rc;
+  // 3. the proofs
+  return actions_prove_core(c, lo, A, w.data(), issue ? 1 : 0, src, proofs + lo);
+}
+
+// The parent checks the whole batch, makes the call's one source, lets every device
+// generate its slice (split as the action provers split) and packs once.
 int generate_device(fts_ctx* c, size_t A, const fts_gen_action* acts, bool issue, uint64_t seed, fts_gen_result* out) {
   if (!c || A > GEN_MAX_ACTIONS || (A && (!acts || !gen_result_valid(out)))) return FTS_API_EINVAL;
   if (A == 0) return FTS_API_OK;
-  if (!c->shards.empty()) c = c->shards[0];  // generation runs on the first device, as the provers do
   if (c->device < 0) return FTS_API_EDEVICE;
   std::vector<size_t> first(A + 1, 0), in_first(A + 1, 0);
   for (size_t i = 0; i < A; i++) {
@@ -110,36 +150,17 @@ int generate_device(fts_ctx* c, size_t A, const fts_gen_action* acts, bool issue
     first[i + 1] = first[i] + acts[i].n_out;
     in_first[i + 1] = in_first[i] + (issue ? 0 : acts[i].n_in);
   }
-  const size_t T = first[A];
-  RngSource src(seed);
+  const RngSource src(seed);
   if (!src.ok) return FTS_API_EDEVICE;
-  // 1. blinding factors (into the caller's array) and the provers' witnesses
-  std::vector<uint64_t> ov(T), iv(in_first[A]);
-  std::vector<uint8_t> ib(32 * in_first[A]);
-  std::vector<uint32_t> owner_of(T);
-  std::vector<fts_action_witness> w(A);
-  parallel_for(A, 256, [&](size_t i) {
-    const fts_gen_action& a = acts[i];
-    gen_draw_bfs(src.at(GEN_BF_STREAM + i), a.n_out, out->bf32 + 32 * first[i]);
-    for (size_t j = 0; j < a.n_out; j++) ov[first[i] + j] = a.outputs[j].value, owner_of[first[i] + j] = (uint32_t)i;
-    const size_t nin = issue ? 0 : a.n_in;
-    for (size_t q = 0; q < nin; q++) {
-      iv[in_first[i] + q] = a.inputs[q].value;
-      memcpy(ib.data() + 32 * (in_first[i] + q), a.inputs[q].bf32, 32);
-    }
-    w[i] = fts_action_witness{a.type, a.type_len, nin, iv.data() + in_first[i], ib.data() + 32 * in_first[i],
-                              a.n_out, ov.data() + first[i], out->bf32 + 32 * first[i]};
+  std::vector<double> wt;
+  if (!c->shards.empty()) {  // no weight for the commitments: 3 fixed-base products per output
+    wt.resize(A);
+    for (size_t i = 0; i < A; i++) wt[i] = action_weight(issue ? 0 : acts[i].n_in, acts[i].n_out, !issue);
+  }
+  std::vector<std::string> proofs(A);
+  int rc = over_devices(c, A, c->shards.empty() ? nullptr : &wt, [&](fts_ctx* ch, size_t lo, size_t hi) {
+    return generate_slice(ch, lo, hi, acts, issue, src, first, in_first, out, proofs.data());
   });
-  // 2. the outputs' commitments (into the caller's array)
-  int rc = token_commit_device(c, T, [&](size_t t, const uint8_t*& type, size_t& type_len, uint64_t& value,
-                                         const uint8_t*& bf32) {
-    const fts_gen_action& a = acts[owner_of[t]];
-    type = a.type, type_len = a.type_len, value = ov[t], bf32 = out->bf32 + 32 * t;
-  }, out->com64);
-  if (rc) return rc;
-  // 3. the proofs
-  std::vector<std::string> proofs;
-  rc = actions_prove_core(c, A, w.data(), issue ? 1 : 0, src, proofs);
   if (rc) return rc;
   // 4. actions and metadata
   return gen_emit(A, acts, issue, proofs, out->com64, out->bf32, *out,
@@ -151,14 +172,16 @@ extern "C" {
 
 int fts_token_commit_batch_gpu(fts_ctx* c, size_t n, const fts_commit_item* items, uint8_t* com64_out) {
   if (!c || n > (size_t)(1u << 26) || (n && (!items || !com64_out))) return FTS_API_EINVAL;
-  if (!c->shards.empty()) c = c->shards[0];
   if (c->device < 0) return FTS_API_EDEVICE;
   for (size_t i = 0; i < n; i++)
     if (!items[i].bf32 || (items[i].type_len && !items[i].type)) return FTS_API_EINVAL;
-  return token_commit_device(c, n, [&](size_t i, const uint8_t*& type, size_t& type_len, uint64_t& value,
-                                       const uint8_t*& bf32) {
-    type = items[i].type, type_len = items[i].type_len, value = items[i].value, bf32 = items[i].bf32;
-  }, com64_out);
+  return over_devices(c, n, nullptr, [&](fts_ctx* ch, size_t lo, size_t hi) {
+    return token_commit_device(ch, hi - lo, [&](size_t i, const uint8_t*& type, size_t& type_len, uint64_t& value,
+                                                const uint8_t*& bf32) {
+      const fts_commit_item& it = items[lo + i];
+      type = it.type, type_len = it.type_len, value = it.value, bf32 = it.bf32;
+    }, com64_out + 64 * lo);
+  });
 }
 
 int fts_token_commit_batch_width(void) { return commit_per_lane() * 64; }

@@ -187,9 +187,9 @@ std::vector<PvStageHost> pv_stage_tables(int n, int k) {
 
 // N range proofs on the device: input(i, value, bf8, rnd) supplies proof i's value, its
 // blinding factor and its 2n + 4 random scalars (canonical limbs, pv_nrnd order);
-// der[i] <- the serialized proof, com64_out[i] (optional) <- V
+// der[i] (N strings) <- the serialized proof, com64_out[i] (optional) <- V
 using PvInput = std::function<void(size_t, uint64_t&, uint32_t*, uint32_t*)>;
-static int rp_prove_device(fts_ctx* c, Lane& L, size_t N, const PvInput& input, std::vector<std::string>& der,
+static int rp_prove_device(fts_ctx* c, Lane& L, size_t N, const PvInput& input, std::string* der,
                            uint8_t* com64_out) {
   const int n = c->n, k = c->k;
   // stage tables (proof-independent), uploaded once per call
@@ -232,7 +232,6 @@ static int rp_prove_device(fts_ctx* c, Lane& L, size_t N, const PvInput& input, 
     stages[s].grp = reinterpret_cast<const int4*>(tb + tb_off[3 * s + 1]);
     stages[s].seg = reinterpret_cast<const int2*>(tb + tb_off[3 * s + 2]);
   }
-  der.assign(N, std::string());
   for (size_t p0 = 0; p0 < N; p0 += B0) {
     const size_t B = std::min(B0, N - p0);
     uint64_t* h_val = reinterpret_cast<uint64_t*>(stg);
@@ -265,6 +264,7 @@ static int rp_prove_device(fts_ctx* c, Lane& L, size_t N, const PvInput& input, 
     d.hslot = base + o_hs;
     const double h1 = now_ms();
     L.tl.begin(L.s);
+    c->st_pv_proofs += (int64_t)B, c->st_pv_passes++;
     launch_rp_prove(d, stages, c->d_x0const.as<uint8_t>(), c->d_x0tmpl.as<uint8_t>(), L.s, &L.tl);
     HIP_OK(hipGetLastError());
     uint8_t* h_pts = stg + in_bytes;
@@ -316,21 +316,24 @@ int fts_rp_prove_batch_gpu(fts_ctx* c, size_t N, const uint64_t* values, const u
   if (!c || !values || !bfs || !out || !offsets || !lens || !com64_out || N > (size_t)(1u << 24))
     return FTS_API_EINVAL;
   if (N == 0) return FTS_API_OK;
-  if (!c->shards.empty())  // provers run on the first device of a multi-device context
-    return fts_rp_prove_batch_gpu(c->shards[0], N, values, bfs, seed, out, out_cap, offsets, lens, com64_out);
   if (c->device < 0) return FTS_API_EDEVICE;
-  HIP_OK(hipSetDevice(c->device));
-  RngSource src(seed);
+  // one source per call, read by every shard: proof g of the call draws from src.at(g)
+  const RngSource src(seed);
   if (!src.ok) return FTS_API_EDEVICE;
-  LaneGuard lg(c);
   const int nr = pv_nrnd(c->n);
-  std::vector<std::string> der;
-  int rc = rp_prove_device(c, *lg.L, N, [&](size_t g, uint64_t& v, uint32_t* bf8, uint32_t* R) {
-    v = values[g];
-    Rng rng = src.at(g);  // the host prover's draw order (prove_range)
-    for (int r = 0; r < nr; r++) fr_canon_words(rng.fr(), R + r * 8);
-    fr_canon_words(fr_from_be(bfs + 32 * g), bf8);
-  }, der, com64_out);
+  std::vector<std::string> der(N);
+  int rc = over_devices(c, N, nullptr, [&](fts_ctx* ch, size_t lo, size_t hi) {
+    if (ch->device < 0) return FTS_API_EDEVICE;
+    HIP_OK(hipSetDevice(ch->device));
+    LaneGuard lg(ch);
+    return rp_prove_device(ch, *lg.L, hi - lo, [&](size_t i, uint64_t& v, uint32_t* bf8, uint32_t* R) {
+      const size_t g = lo + i;
+      v = values[g];
+      Rng rng = src.at(g);  // the host prover's draw order (prove_range)
+      for (int r = 0; r < nr; r++) fr_canon_words(rng.fr(), R + r * 8);
+      fr_canon_words(fr_from_be(bfs + 32 * g), bf8);
+    }, der.data() + lo, com64_out + 64 * lo);
+  });
   if (rc) return rc;
   size_t off = 0;
   for (size_t i = 0; i < N; i++) {
@@ -350,21 +353,18 @@ int fts_rp_prove_batch_gpu(fts_ctx* c, size_t N, const uint64_t* values, const u
 // range proofs of every output (rp_prove_device), byte-identical to
 // fts_transfer_prove / fts_issue_prove for the same seeds
 // ---------------------------------------------------------------------------
-int actions_prove_core(fts_ctx* c, size_t A, const fts_action_witness* w, int issue, const RngSource& src,
-                       std::vector<std::string>& der) {
-  if (!c || !w || A > (size_t)(1u << 22)) return FTS_API_EINVAL;
-  der.assign(A, std::string());
+bool action_witness_valid(const fts_action_witness& x, int issue) {
+  const size_t nin = issue ? 0 : x.n_in;
+  return !((!issue && (!nin || !x.in_values || !x.in_bfs)) || !x.n_out || !x.out_values || !x.out_bfs ||
+           (x.type_len && !x.type) || nin > 4096 || x.n_out > 4096);
+}
+
+int actions_prove_core(fts_ctx* c, size_t g0, size_t A, const fts_action_witness* w, int issue,
+                       const RngSource& src, std::string* der) {
+  if (!c || !w || !der || A > (size_t)(1u << 22)) return FTS_API_EINVAL;
   if (A == 0) return FTS_API_OK;
-  if (c->device < 0) return FTS_API_EDEVICE;
+  if (c->device < 0 || !src.ok) return FTS_API_EDEVICE;
   const int n = c->n, nr = pv_nrnd(n), kind = issue ? 1 : 0;
-  for (size_t a = 0; a < A; a++) {
-    const fts_action_witness& x = w[a];
-    const size_t nin = issue ? 0 : x.n_in;
-    if ((!issue && (!nin || !x.in_values || !x.in_bfs)) || !x.n_out || !x.out_values || !x.out_bfs ||
-        (x.type_len && !x.type) || nin > 4096 || x.n_out > 4096)
-      return FTS_API_EINVAL;
-  }
-  if (!src.ok) return FTS_API_EDEVICE;
   HIP_OK(hipSetDevice(c->device));
   LaneGuard lg(c);
   Lane& L = *lg.L;
@@ -393,7 +393,7 @@ int actions_prove_core(fts_ctx* c, size_t A, const fts_action_witness* w, int is
     const fts_action_witness& x = w[a];
     const SpAction& ac = act[a];
     uint32_t* S = h_sc.data() + (size_t)ac.sc_off * 8;
-    Rng rng = src.at(a);
+    Rng rng = src.at(g0 + a);  // the action's index in the caller's batch
     const Fr type = type_to_zr(x.type, x.type_len);
     const Fr tbf = rng.fr();
     fr_canon_words(type, S);
@@ -449,19 +449,20 @@ int actions_prove_core(fts_ctx* c, size_t A, const fts_action_witness* w, int is
   d.be = base + o_be;
   d.msgs = base + o_msg;
   d.out = reinterpret_cast<uint32_t*>(base + o_out);
+  c->st_pv_actions += (int64_t)A, c->st_pv_passes++;
   launch_sigma_prove(d, L.s);
   HIP_OK(hipGetLastError());
   HIP_OK(hipMemcpyAsync(h_be.data(), base + o_be, npt * 64, hipMemcpyDeviceToHost, L.s));
   HIP_OK(hipMemcpyAsync(h_out.data(), base + o_out, nout * 32, hipMemcpyDeviceToHost, L.s));
   HIP_OK(L.sync());
   // device: every range proof of the batch
-  std::vector<std::string> rps;
+  std::vector<std::string> rps(NR);
   if (NR) {
     int rc = rp_prove_device(c, L, NR, [&](size_t r, uint64_t& v, uint32_t* bf8, uint32_t* R) {
       v = rp_val[r];
       memcpy(bf8, rp_bf.data() + r * 8, 32);
       memcpy(R, rp_rnd.data() + r * nr * 8, (size_t)nr * 32);
-    }, rps, nullptr);
+    }, rps.data(), nullptr);
     if (rc) return rc;
   }
   // host: DER (transfer.go:140-149 / issue/prover.go:100-111)
@@ -494,14 +495,27 @@ int actions_prove_core(fts_ctx* c, size_t A, const fts_action_witness* w, int is
   return FTS_API_OK;
 }
 
+// The whole batch is checked before any device starts; a multi-device context then splits it
+// by the verify side's action weights, every child proving its slice into der at the slice's
+// offset with the call's one source, and the parent packs once.
 static int actions_prove_device(fts_ctx* c, size_t A, const fts_action_witness* w, int issue, uint64_t seed,
                                 uint8_t* out, size_t out_cap, size_t* offsets, size_t* lens) {
   if (!c || !w || !out || !offsets || !lens || A > (size_t)(1u << 22)) return FTS_API_EINVAL;
   if (A == 0) return FTS_API_OK;
   if (c->device < 0) return FTS_API_EDEVICE;
-  RngSource src(seed);
-  std::vector<std::string> der;
-  int rc = actions_prove_core(c, A, w, issue, src, der);
+  for (size_t a = 0; a < A; a++)
+    if (!action_witness_valid(w[a], issue)) return FTS_API_EINVAL;
+  const RngSource src(seed);
+  if (!src.ok) return FTS_API_EDEVICE;
+  std::vector<double> wt;
+  if (!c->shards.empty()) {
+    wt.resize(A);
+    for (size_t a = 0; a < A; a++) wt[a] = action_weight(issue ? 0 : w[a].n_in, w[a].n_out, !issue);
+  }
+  std::vector<std::string> der(A);
+  int rc = over_devices(c, A, c->shards.empty() ? nullptr : &wt, [&](fts_ctx* ch, size_t lo, size_t hi) {
+    return actions_prove_core(ch, lo, hi - lo, w + lo, issue, src, der.data() + lo);
+  });
   if (rc) return rc;
   size_t off = 0;
   for (size_t a = 0; a < A; a++) {
@@ -517,12 +531,10 @@ static int actions_prove_device(fts_ctx* c, size_t A, const fts_action_witness* 
 extern "C" {
 int fts_transfer_prove_batch_gpu(fts_ctx* c, size_t n, const fts_action_witness* w, uint64_t seed, uint8_t* out,
                                  size_t out_cap, size_t* offsets, size_t* lens) {
-  if (c && !c->shards.empty()) c = c->shards[0];
   return actions_prove_device(c, n, w, 0, seed, out, out_cap, offsets, lens);
 }
 int fts_issue_prove_batch_gpu(fts_ctx* c, size_t n, const fts_action_witness* w, uint64_t seed, uint8_t* out,
                               size_t out_cap, size_t* offsets, size_t* lens) {
-  if (c && !c->shards.empty()) c = c->shards[0];
   return actions_prove_device(c, n, w, 1, seed, out, out_cap, offsets, lens);
 }
 }  // extern "C"

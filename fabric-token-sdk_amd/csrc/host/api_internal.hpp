@@ -375,6 +375,9 @@ struct fts_ctx {
   // range-proof pass counters (fts_debug_pass_stats): passes finished, passes whose
   // combination did not close, locator hits, proofs given to the per-proof equations
   std::atomic<int64_t> st_rp_passes{0}, st_rp_failed{0}, st_rp_located{0}, st_rp_perproof{0};
+  // prover-side work counters (fts_debug_shard_work), bumped next to the launches: range
+  // proofs proved, sigma proofs (actions), tokens committed, prover / commit passes started
+  std::atomic<int64_t> st_pv_proofs{0}, st_pv_actions{0}, st_pv_tokens{0}, st_pv_passes{0};
   // passes of up to com_fixed_max proofs compute com on the latency path (fixed-base
   // groups, rp_exact.hip k_rp_fixed_all), larger ones on the work path (Horner +
   // joint GLV chains): the same group element either way
@@ -496,10 +499,14 @@ int lane_reserve(fts_ctx* c, Lane& L, int B, bool inputs);
 int rp_dispatch(fts_ctx* c, RpReq& me);
 // the context's host prover tables, built on first use [api_prove.cpp]
 const ProverTables& prover_tables(const fts_ctx* cc);
-// A whole transfer (issue = 0) / issue proofs on one device context, action a drawing
-// from src.at(a): der[a] <- the proof of fts_transfer_prove / fts_issue_prove [api_prove.cpp]
-int actions_prove_core(fts_ctx* c, size_t A, const fts_action_witness* w, int issue, const RngSource& src,
-                       std::vector<std::string>& der);
+// the argument checks of the action provers on one witness [api_prove.cpp]
+bool action_witness_valid(const fts_action_witness& x, int issue);
+// A whole transfer (issue = 0) / issue proofs on one device context: w[a] is item g0 + a
+// of its call and draws from src.at(g0 + a) -- the index in the caller's batch, never the
+// one inside a shard; der[a] <- the proof of fts_transfer_prove / fts_issue_prove.  The
+// caller has checked every witness (action_witness_valid / gen_valid) [api_prove.cpp]
+int actions_prove_core(fts_ctx* c, size_t g0, size_t A, const fts_action_witness* w, int issue,
+                       const RngSource& src, std::string* der);
 // n token commitments on one device context: item(i, type, type_len, value, bf32) names
 // token i; com64_out[i] <- its 64 bytes [api_generate.cpp]
 using CommitItem = std::function<void(size_t, const uint8_t*&, size_t&, uint64_t&, const uint8_t*&)>;
@@ -522,6 +529,15 @@ inline std::vector<size_t> plan(size_t n, const std::vector<double>* w, int ns) 
   std::vector<size_t> b(ns + 1);
   fts_shard_plan(n, w ? w->data() : nullptr, ns, b.data());
   return b;
+}
+
+// f(child, lo, hi) for the slice [lo, hi) of n items on every child of a multi-device
+// context (split by the weights w, NULL: equal), concurrently; f(c, 0, n) on any other
+template <class F>
+int over_devices(fts_ctx* c, size_t n, const std::vector<double>* w, F&& f) {
+  if (c->shards.empty()) return f(c, (size_t)0, n);
+  return run_shards(plan(n, w, (int)c->shards.size()),
+                    [&](int j, size_t lo, size_t hi) { return f(c->shards[j], lo, hi); });
 }
 
 // cost weight of an action: its range proofs (none for a 1-in/1-out transfer) + the sigma proof

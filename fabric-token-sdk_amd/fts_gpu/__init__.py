@@ -184,6 +184,25 @@ class PublicParams:
         L.check("fts_debug_pass_stats", L.lib.fts_debug_pass_stats(self._ctx, out))
         return tuple(out)
 
+    def shard_work(self, shard=0):
+        """(range proofs proved, sigma proofs, tokens committed, prover / commit passes
+        started) on one child of a multi-device context since creation
+        (fts_debug_shard_work); a single-device context is shard 0 of itself"""
+        out = (C.c_int64 * 4)()
+        L.check("fts_debug_shard_work", L.lib.fts_debug_shard_work(self._ctx, int(shard), out))
+        return tuple(out)
+
+    def shard_timings(self, shard=0):
+        """{name: ms} of the pass that finished last on one child (fts_debug_shard_timings):
+        last_timings() of that child, host phases included"""
+        names = (C.c_char_p * 64)()
+        ms = (C.c_float * 64)()
+        m = L.lib.fts_debug_shard_timings(self._ctx, int(shard), names, ms, 64)
+        out = {}
+        for i in range(m):
+            out[names[i].decode()] = out.get(names[i].decode(), 0.0) + ms[i]
+        return out
+
     def table_info(self, shard=0):
         """fts_ctx_table_info: the table-cache entries this context (its shard `shard`
         on a multi-device context) reads -> :class:`TableInfo`.  Equal ids on one

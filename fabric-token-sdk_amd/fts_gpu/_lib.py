@@ -75,7 +75,7 @@ EXPORTED = [
     "fts_idemix_ipk_create", "fts_idemix_ipk_destroy", "fts_nym_verify_batch", "fts_idemix_identity_nym",
     "fts_nym_last_timings", "fts_idemix_idv_create", "fts_idemix_idv_destroy", "fts_idemix_identity_verify_batch",
     "fts_idemix_identity_last_timings", "fts_idemix_identity_last_stats", "fts_idemix_pairing_debug", "fts_ctx_create_opts", "fts_debug_hold",
-    "fts_debug_dispatch_stats", "fts_debug_pass_stats", "fts_debug_stage_actions",
+    "fts_debug_dispatch_stats", "fts_debug_pass_stats", "fts_debug_shard_work", "fts_debug_shard_timings", "fts_debug_stage_actions",
     "fts_idemix_audit_match_batch", "fts_idemix_audit_last_timings",
     "fts_ctx_table_info", "fts_table_cache_stats",
     "fts_token_commit_batch_gpu", "fts_token_commit_batch_width", "fts_transfer_generate", "fts_issue_generate",
@@ -196,6 +196,8 @@ def _load():
         "fts_debug_hold": ([P, C.c_int], C.c_int),
         "fts_debug_dispatch_stats": ([P, C.POINTER(C.c_int64)], C.c_int),
         "fts_debug_pass_stats": ([P, C.POINTER(C.c_int64)], C.c_int),
+        "fts_debug_shard_work": ([P, C.c_int, C.POINTER(C.c_int64)], C.c_int),
+        "fts_debug_shard_timings": ([P, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_float), C.c_int], C.c_int),
         "fts_debug_stage_actions": ([P, S, C.POINTER(TransferItem), S, C.POINTER(IssueItem), C.c_int,
                                      C.POINTER(C.c_float)], C.c_int),
         "fts_rp_verify_batch": ([P, S, C.POINTER(C.c_void_p), C.POINTER(S), U8P, I32P], C.c_int),

@@ -167,7 +167,18 @@ int fts_ctx_create_opts(const uint8_t* pp, size_t pp_len, int device, const fts_
  * into contiguous shards balanced by cost (fts_shard_plan: range proofs per action),
  * runs the shards on their devices concurrently and returns the verdicts in the
  * caller's order; fts_msm_g1 sums the devices' partial MSM points on the host.
- * Provers, staged MSMs, timings and debug hooks use the first device.  devices[] may
+ * The device provers, fts_token_commit_batch_gpu and the generators split the same way
+ * (proofs and tokens equally, actions by the verify side's weights) and write their
+ * results in the caller's order.  Their randomness keeps its GLOBAL index: one source per
+ * call, item g of the caller's batch draws from stream g on whichever device it runs, so
+ * a seeded call gives the single-device bytes and a secure call never uses one
+ * (key, stream) pair for two items.  The whole batch is checked before any device starts;
+ * the first error in shard order is returned.
+ * Not sharded, first device only: staged MSMs (fts_msm_stage*, fts_msm_run,
+ * fts_msm_points: a handle would have to span devices), fts_last_timings* and the debug
+ * hooks.  The randomness draws and the DER / protobuf writers run on the one host pool
+ * for all devices.  The ECDSA, nym and identity calls take a device ordinal or a
+ * per-device handle; their callers shard them.  devices[] may
  * repeat an ordinal (several shards on one device).  bit_length 0: the PP's own. */
 int fts_ctx_create_devices(const uint8_t* pp, size_t pp_len, uint32_t bit_length, const int32_t* devices, int ndev,
                            fts_ctx** out);
@@ -299,6 +310,18 @@ int fts_debug_dispatch_stats(const fts_ctx* ctx, int64_t* out);
  * (1, 0, 0, 0): a fallback gives the right verdicts whatever the main path computed,
  * so only out[1] shows that the main path is sound. */
 int fts_debug_pass_stats(const fts_ctx* ctx, int64_t out[4]);
+/* prover-side work of ONE child of a multi-device context since context creation (shard:
+ * index into the context's devices; a single-device context is shard 0 of itself):
+ * out[0] range proofs proved on it, out[1] sigma proofs (actions), out[2] tokens
+ * committed, out[3] prover or commit passes started.  Shows that a call ran on every
+ * device, which equal output bytes cannot.  FTS_API_EINVAL for a host-only context or a
+ * shard out of range. */
+int fts_debug_shard_work(const fts_ctx* ctx, int shard, int64_t out[4]);
+/* fts_last_timings of ONE child (fts_last_timings itself reads the first): the kernel
+ * classes and the host phases (host_prep: randomness staged, host_wait_flag: device,
+ * host_parse: DER) of the pass that finished last on it; returns the count filled, 0 for a
+ * shard out of range.  tools/prove_multi_bench.py reads the host share per device here. */
+int fts_debug_shard_timings(const fts_ctx* ctx, int shard, const char** names, float* ms, int cap);
 /* per-kernel device time (ms) and algorithmic u32 MADs of b's last verification */
 int fts_rp_batch_timings(const fts_rp_batch* b, const char** names, float* ms, double* mads, int cap);
 void fts_rp_batch_free(fts_rp_batch* b);
@@ -387,7 +410,10 @@ const char* fts_status_str(int32_t status);
  *   any other value     deterministic, FOR TESTS AND BENCHMARKS ONLY: item i draws from
  *                       xoshiro256**(seed + i).  Two calls whose seed ranges overlap reuse
  *                       nonces across different witnesses, which reveals the committed
- *                       values and blinding factors. */
+ *                       values and blinding factors.
+ * i is the item's index in the caller's batch.  A multi-device context keeps it: its
+ * shards read the call's one source (one getrandom() key in secure mode) at the global
+ * index, never at the index inside the shard. */
 #define FTS_SEED_OS_RANDOM UINT64_MAX
 /* value < 2^bit_length expected (larger values produce a proof that fails, as in the
  * reference).  bf32: blinding factor (BE, reduced mod r).  seed: deterministic RNG seed.
@@ -404,7 +430,9 @@ int fts_rp_prove_batch(const fts_ctx* ctx, size_t n, const uint64_t* values, con
  * proofs in device passes of up to 16,384 (prove_kernels.hip).  Same arguments and output as
  * fts_rp_prove_batch -- byte-identical proofs for the same seed (proof i uses seed + i; the
  * host draws the randomness, the device computes every group element, transcript and
- * Fiat-Shamir challenge).  Needs a device context. */
+ * Fiat-Shamir challenge).  Needs a device context.  A multi-device context proves an equal
+ * share on every device, proof i still from seed + i (its index in this call), and packs the
+ * proofs in the caller's order: the same bytes, offsets and lengths as on one device. */
 int fts_rp_prove_batch_gpu(fts_ctx* ctx, size_t n, const uint64_t* values, const uint8_t* bfs, uint64_t seed,
                            uint8_t* out, size_t out_cap, size_t* offsets, size_t* lens, uint8_t* com64_out);
 /* Whole transfer / issue proofs on the device: the TypeAndSum
@@ -412,7 +440,10 @@ int fts_rp_prove_batch_gpu(fts_ctx* ctx, size_t n, const uint64_t* values, const
  * proof in one kernel (thread per action), then the range proofs of every output of every
  * action in one fts_rp_prove_batch_gpu-style pass.  Action i is seeded with seed + i and the
  * output is byte-identical to fts_transfer_prove / fts_issue_prove.  Issues ignore n_in /
- * in_values / in_bfs (their tokens are the outputs). */
+ * in_values / in_bfs (their tokens are the outputs).  A multi-device context splits the
+ * actions as the verify entry points do (by range proofs per action); i stays the action's
+ * index in this call, so the output does not depend on the devices.  Every witness is
+ * checked before any device starts (FTS_API_EINVAL, no device work). */
 typedef struct {
   const uint8_t* type;
   size_t type_len;
@@ -444,7 +475,7 @@ int fts_issue_prove(const fts_ctx* ctx, const uint8_t* type, size_t type_len, si
  * byte-identical to fts_token_commit on the same arguments (bf32: 32 B BE, used mod r; the
  * identity comes out as 64 zero bytes).  Three fixed-base products per token into one
  * accumulator, then the exact affine point.  Needs a device context (FTS_API_EDEVICE
- * otherwise); a multi-device context runs it on its first device, as the provers do. */
+ * otherwise); a multi-device context commits an equal share of the tokens on every device. */
 typedef struct {
   const uint8_t* type;
   size_t type_len;
@@ -522,7 +553,12 @@ int fts_transfer_generate(const fts_ctx* ctx, const fts_gen_action* action, uint
 int fts_issue_generate(const fts_ctx* ctx, const fts_gen_action* action, uint64_t seed, fts_gen_result* out);
 /* n actions on the device: commitments by k_token_commit, proofs by the passes of
  * fts_transfer_prove_batch_gpu / fts_issue_prove_batch_gpu, serialization on the host pool.
- * Action i equals the host call at seed + i.  Needs a device context (FTS_API_EDEVICE). */
+ * Action i equals the host call at seed + i.  Needs a device context (FTS_API_EDEVICE).
+ * A multi-device context splits the actions as the action provers do; action i (its index
+ * in this call) keeps prover stream i and blinding-factor stream 2^63 + i and its outputs
+ * their numbers across the call, every device writes com64 / bf32 at those offsets, and the
+ * actions and metadata are packed once: output and FTS_API_ESIZE behaviour are those of one
+ * device. */
 int fts_transfer_generate_batch_gpu(fts_ctx* ctx, size_t n, const fts_gen_action* actions, uint64_t seed,
                                     fts_gen_result* out);
 int fts_issue_generate_batch_gpu(fts_ctx* ctx, size_t n, const fts_gen_action* actions, uint64_t seed,
