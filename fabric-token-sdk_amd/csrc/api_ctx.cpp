@@ -429,6 +429,34 @@ int fts_ctx_table_info(const fts_ctx* c, int shard, fts_table_info* o) {
   return FTS_API_OK;
 }
 
+// debug: entries T[w][d - 1] of one base's table as the device holds them (the tables
+// are read-only once built, so the copies need no lane), 64-byte X||Y BE each
+int fts_debug_table_entries(fts_ctx* c, int wide, int base, size_t count, const uint32_t* w, const uint32_t* d,
+                            uint8_t* out64) {
+  if (c && !c->shards.empty()) return fts_debug_table_entries(c->shards[0], wide, base, count, w, d, out64);
+  if (!c || c->device < 0 || !c->d_tables.e || !c->d_wtables.e) return FTS_API_EINVAL;
+  if (count && (!w || !d || !out64)) return FTS_API_EINVAL;
+  const int bits = wide ? c->wbits : 16;
+  const int nbases = wide ? c->n + 2 : 2 * c->n + 6;
+  const size_t nw = (size_t)(255 + bits - 1) / bits, e = (size_t)1 << (bits - 1);
+  const size_t per_base = wide ? fbw_words_per_base(bits) : fb_words_per_base();
+  if (base < 0 || base >= nbases) return FTS_API_EINVAL;
+  for (size_t j = 0; j < count; j++)
+    if (w[j] >= nw || d[j] < 1 || d[j] > e) return FTS_API_EINVAL;
+  const uint32_t* t = (wide ? c->d_wtables : c->d_tables).as<uint32_t>() + (size_t)base * per_base;
+  HIP_OK(hipSetDevice(c->device));
+  for (size_t j = 0; j < count; j++) {
+    uint32_t m[16];
+    HIP_OK(hipMemcpy(m, t + ((size_t)w[j] * e + d[j] - 1) * 16, 64, hipMemcpyDeviceToHost));
+    G1A a{};
+    memcpy(a.x.v, m, 32);  // 8x32 LE == 4x64 LE Montgomery form
+    memcpy(a.y.v, m + 8, 32);
+    a.inf = false;
+    g1_to_bytes(a, out64 + 64 * j);
+  }
+  return FTS_API_OK;
+}
+
 int fts_debug_shard_work(const fts_ctx* c, int shard, int64_t out[4]) {
   if (!c || !out) return FTS_API_EINVAL;
   if (!c->shards.empty()) {

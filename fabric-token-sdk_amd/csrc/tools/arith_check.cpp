@@ -7,6 +7,17 @@
 //   arith_check --list   the op catalogue ("name operands results"), no device
 //   arith_check --list-chain   the same for the com chain's op (straus4_ctab:
 //                        tests/com_chain_vectors.py), kept apart from the primitives' list
+//   arith_check --list-fb      the same for the fixed-base ops (tests/fixed_base_vectors.py):
+//                        the signed-digit recoding and the table products of fixed_base.hpp
+//
+// A fixed-base product's record carries, after its device operands, the table entries
+// its scalar selects: per table and window three words |d| x y, the affine Montgomery
+// point |d| * 2^(W w) * B that the test computed, or 0 0 0 for a zero digit.  The tool
+// scatters them to (w * E + |d| - 1) * 16 of a table of the production size that is
+// otherwise 0xFF bytes, guard windows before and after included (SparseTable below),
+// so a device that looks anywhere else reads poison, inside the allocation.  All
+// records of an op share its table(s): two that place different points at one position
+// violate the contract.
 //
 // An operand or result is one 256-bit word in hex (most significant digit first):
 // the 8 little-endian uint32 limbs exactly as the device function takes and
@@ -26,6 +37,8 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <array>
+#include <map>
 #include <string>
 #include <vector>
 #include "../device/glv.hpp"
@@ -109,6 +122,7 @@ FTS_DEV void st12(uint32_t* r, int w, const pair::F12<B>& x) {
     static FTS_DEV void run(const uint32_t* a, uint32_t* r, const Aux& x, size_t i) { __VA_ARGS__ } \
   }
 #define TOP(T, NAME, NI, NO, ...) template <class T> OP(NAME, NI, NO, __VA_ARGS__)
+#define TOP_W(W, NAME, NI, NO, ...) template <int W> OP(NAME, NI, NO, __VA_ARGS__)
 
 // BN254 Fp / Fr (field.hpp)
 TOP(P, FAdd, 2, 1, using F = fts::Field<P>; st(r, 0, fts::f_add(ld<F>(a, 0), ld<F>(a, 1))););
@@ -158,6 +172,41 @@ OP(Straus4Ctab, 13, 3, const fts::CTab T{x.tab, x.n, i}; const fts::G1A D = lda(
    const bool idD = fts::g1a_is_identity(D); const bool idS = fts::f_is_zero(S.z);
    fts::ctab_build8<true>(T, 0, fts::g1j_from_affine(D), idD); fts::ctab_build8<false>(T, 8, S, idS);
    stj(r, fts::straus4_ctab(T, a + 40, a[48] != 0, a + 56, a[64] != 0, a + 72, a[80] != 0, a + 88, a[96] != 0, idD, idS)););
+
+// fixed-base digits and table products (fixed_base.hpp).  The digit ops call the
+// recoding as the products do (a copy of k shifted in place, carry 0 in) and return
+// the NW digits, each as the int's 32 bits in limb 0, then the carry out.  The
+// products read the op's sparse table(s), x.tab and for fb_mul2's second base x.scr
+template <int W>
+struct FbDigitsW {
+  static constexpr int ni = 1, no = fts::FbCfg<W>::NW + 1;
+  static FTS_DEV void run(const uint32_t* a, uint32_t* r, const Aux&, size_t) {
+    uint32_t s[8];
+#pragma unroll
+    for (int q = 0; q < 8; q++) s[q] = a[q];
+    int carry = 0;
+#pragma unroll
+    for (int w = 0; w < fts::FbCfg<W>::NW; w++) stw(r, w, (uint32_t)fts::fb_next_digit_w<W>(s, carry));
+    stw(r, fts::FbCfg<W>::NW, (uint32_t)carry);
+  }
+};
+struct FbDigits16 {  // fb_next_digit, the 16-bit tables' own copy (fb_mul2, fb_mul_acc_jac)
+  static constexpr int ni = 1, no = fts::FB_NW + 1;
+  static FTS_DEV void run(const uint32_t* a, uint32_t* r, const Aux&, size_t) {
+    uint32_t s[8];
+#pragma unroll
+    for (int q = 0; q < 8; q++) s[q] = a[q];
+    int carry = 0;
+#pragma unroll
+    for (int w = 0; w < fts::FB_NW; w++) stw(r, w, (uint32_t)fts::fb_next_digit(s, carry));
+    stw(r, fts::FB_NW, (uint32_t)carry);
+  }
+};
+TOP_W(W, FbSumW, 1, 4, stx(r, fts::fb_sum_w<W>(x.tab, ld<fts::Scalar>(a, 0))););
+TOP_W(W, FbMulW, 1, 3, stj(r, fts::fb_mul_w<W>(x.tab, ld<fts::Scalar>(a, 0))););
+OP(FbMul2, 2, 3, stj(r, fts::fb_mul2(x.tab, ld<fts::Scalar>(a, 0), x.scr, ld<fts::Scalar>(a, 1))););
+OP(FbMulAcc, 4, 3, fts::G1J p = ldj(a, 0); fts::fb_mul_acc(p, x.tab, ld<fts::Scalar>(a, 3)); stj(r, p););
+OP(FbMulAccJac, 4, 3, fts::G1J p = ldj(a, 0); fts::fb_mul_acc_jac(p, x.tab, ld<fts::Scalar>(a, 3)); stj(r, p););
 
 // GLV decomposition (glv.hpp): k -> |k1|, s1, |k2|, s2
 TOP(K, GlvDec, 1, 4, uint32_t k1[4]; uint32_t k2[4]; uint32_t s1; uint32_t s2; fts::glv_decompose<K>(a, k1, s1, k2, s2);
@@ -283,6 +332,9 @@ struct Entry {
   bool (*check)(const uint32_t*);  // whole-record contract, or null
   bool aux;                      // uses the lane tables
   void (*fn)(const uint32_t*, uint32_t*, int, Aux);
+  int fbw = 0, fbt = 0;          // fixed-base op: window width and tables (0: none)
+  // a record's words: the ni device operands, then per table and window the entry |d| x y
+  int nwords() const { return ni + (fbw ? 3 * ((255 + fbw - 1) / fbw) * fbt : 0); }
 };
 template <class Op>
 static Entry E(const char* name, const char* spec, bool (*check)(const uint32_t*) = nullptr, bool aux = false) {
@@ -394,6 +446,64 @@ static std::vector<Entry> chain_ops() {
   return c;
 }
 
+// the fixed-base ops: listed by --list-fb (tests/fixed_base_vectors.py), apart from the
+// primitives' catalogue for the reason chain_ops gives.  fb_mul2_same and fb_mul2_neg are
+// fb_mul2 under names of their own, so that each has tables of its own (the second a
+// table of the first's base, resp. of its negative: the vectors' business)
+template <class Op>
+static Entry FB(const char* name, const char* spec, int w, int tabs, bool (*check)(const uint32_t*) = nullptr) {
+  Entry e = E<Op>(name, spec, check);
+  e.fbw = w, e.fbt = tabs;
+  return e;
+}
+static std::vector<Entry> fb_ops() {
+  std::vector<Entry> c;
+  c.push_back(E<FbDigits16>("fb_digits_16", "1"));
+  c.push_back(E<FbDigitsW<16>>("fb_digits_w16", "1"));
+  c.push_back(E<FbDigitsW<20>>("fb_digits_20", "1"));
+  c.push_back(E<FbDigitsW<22>>("fb_digits_22", "1"));
+  c.push_back(FB<FbSumW<16>>("fb_sum_16", "1", 16, 1));
+  c.push_back(FB<FbSumW<20>>("fb_sum_20", "1", 20, 1));
+  c.push_back(FB<FbSumW<22>>("fb_sum_22", "1", 22, 1));
+  c.push_back(FB<FbMulW<16>>("fb_mul_16", "1", 16, 1));
+  c.push_back(FB<FbMulW<20>>("fb_mul_20", "1", 20, 1));
+  c.push_back(FB<FbMulW<22>>("fb_mul_22", "1", 22, 1));
+  c.push_back(FB<FbMul2>("fb_mul2", "11", 16, 2));
+  c.push_back(FB<FbMul2>("fb_mul2_same", "11", 16, 2));
+  c.push_back(FB<FbMul2>("fb_mul2_neg", "11", 16, 2));
+  c.push_back(FB<FbMulAcc>("fb_mul_acc", "0001", 16, 1, &chk_jac0));
+  c.push_back(FB<FbMulAccJac>("fb_mul_acc_jac", "0001", 16, 1, &chk_jac0));
+  return c;
+}
+
+// a sparse fixed-base table on the device: the production size and layout of one base
+// (FbCfg<W>::WORDS_PER_BASE) between two guard windows, every byte 0xFF but the entries
+// the records supply, so a lookup at any other (window, digit) reads poison -- inside
+// the allocation -- and the result differs
+struct SparseTable {
+  int W, NW;
+  size_t E;
+  std::map<size_t, std::array<uint32_t, 16>> rows;  // row w * E + |d| - 1
+  uint32_t* dev = nullptr;
+  explicit SparseTable(int w) : W(w), NW((255 + w - 1) / w), E((size_t)1 << (w - 1)) {}
+  // false: another record placed a different point there
+  bool put(int w, uint32_t d, const uint32_t* xy) {
+    std::array<uint32_t, 16> v;
+    memcpy(v.data(), xy, 64);
+    auto it = rows.emplace((size_t)w * E + d - 1, v);
+    return it.second || it.first->second == v;
+  }
+  size_t bytes() const { return ((size_t)NW + 2) * E * 64; }
+  uint32_t* upload() {  // the table proper starts one window in
+    CK(hipMalloc(&dev, bytes()));
+    CK(hipMemset(dev, 0xFF, bytes()));
+    for (const auto& kv : rows)
+      CK(hipMemcpy(dev + (E + kv.first) * 16, kv.second.data(), 64, hipMemcpyHostToDevice));
+    return dev + E * 16;
+  }
+  void release() { CK(hipFree(dev)); }
+};
+
 // ------------------------------------------------------------------- host: io
 static bool parse_word(const char* s, uint32_t w[8]) {
   const size_t len = strlen(s);
@@ -413,12 +523,13 @@ static bool parse_word(const char* s, uint32_t w[8]) {
 
 struct Batch {
   std::vector<uint32_t> in;
+  std::vector<SparseTable> tabs;  // fixed-base ops: filled from the records' entries
   std::vector<size_t> rec;  // output position of each record
 };
 
 int main(int argc, char** argv) {
   std::vector<Entry> cat = catalogue();
-  const std::vector<Entry> chain = chain_ops();
+  const std::vector<Entry> chain = chain_ops(), fb = fb_ops();
   if (argc == 2 && !strcmp(argv[1], "--list")) {
     for (const Entry& e : cat) printf("%s %d %d\n", e.name, e.ni, e.no);
     return 0;
@@ -427,9 +538,14 @@ int main(int argc, char** argv) {
     for (const Entry& e : chain) printf("%s %d %d\n", e.name, e.ni, e.no);
     return 0;
   }
+  if (argc == 2 && !strcmp(argv[1], "--list-fb")) {
+    for (const Entry& e : fb) printf("%s %d %d\n", e.name, e.nwords(), e.no);
+    return 0;
+  }
   cat.insert(cat.end(), chain.begin(), chain.end());
+  cat.insert(cat.end(), fb.begin(), fb.end());
   if (argc != 3) {
-    fprintf(stderr, "usage: %s IN OUT | --list | --list-chain\n", argv[0]);
+    fprintf(stderr, "usage: %s IN OUT | --list | --list-chain | --list-fb\n", argv[0]);
     return 2;
   }
   FILE* fi = fopen(argv[1], "r");
@@ -466,8 +582,32 @@ int main(int argc, char** argv) {
           return 2;
         }
       }
+      if (e.fbw && b.tabs.empty()) b.tabs.assign((size_t)e.fbt, SparseTable(e.fbw));
+      for (SparseTable& t : b.tabs)
+        for (int w = 0; w < t.NW; w++) {
+          uint32_t ent[24];  // |d| x y: d = 0 with x = y = 0, or 1 <= d <= E with a curve point
+          for (int q = 0; q < 3; q++) {
+            const char* tok = strtok_r(nullptr, " \t\r\n", &save);
+            if (!tok || !parse_word(tok, ent + 8 * q)) {
+              fprintf(stderr, "line %zu: %s takes %d words\n", ln, op, e.nwords());
+              return 2;
+            }
+          }
+          const bool none = upper_zero(ent, 0) && upper_zero(ent + 8, 0) && upper_zero(ent + 16, 0);
+          if (none) continue;
+          if (!upper_zero(ent, 1) || ent[0] == 0 || ent[0] > t.E || !word_ok('0', ent + 8) || !word_ok('0', ent + 16) ||
+              !jac_on_curve(hfp(ent + 8), hfp(ent + 16), fts::host::Fp::one())) {
+            fprintf(stderr, "line %zu: %s window %d: not a table entry\n", ln, op, w);
+            return 2;
+          }
+          if (!t.put(w, ent[0], ent + 8)) {
+            fprintf(stderr, "line %zu: %s window %d digit %u: another record placed a different point there\n", ln, op,
+                    w, ent[0]);
+            return 2;
+          }
+        }
       if (strtok_r(nullptr, " \t\r\n", &save)) {
-        fprintf(stderr, "line %zu: %s takes %d operand words\n", ln, op, e.ni);
+        fprintf(stderr, "line %zu: %s takes %d words\n", ln, op, e.nwords());
         return 2;
       }
       if (e.check && !e.check(&b.in[base])) {
@@ -498,6 +638,9 @@ int main(int argc, char** argv) {
       CK(hipMalloc(&x.tab, n * (size_t)fts::CTAB_WORDS * 4));  // >= 16 * 24 words per lane
       CK(hipMalloc(&x.scr, n * 10 * 24 * 4));
     }
+    std::vector<SparseTable> tabs = b.tabs;
+    if (tabs.size() > 0) x.tab = tabs[0].upload();
+    if (tabs.size() > 1) x.scr = tabs[1].upload();
     CK(hipMemcpy(din, b.in.data(), b.in.size() * 4, hipMemcpyHostToDevice));
     CK(hipMemset(dout, 0, out_words * 4));
     e.fn(din, dout, (int)n, x);
@@ -513,6 +656,7 @@ int main(int argc, char** argv) {
       CK(hipFree(x.tab));
       CK(hipFree(x.scr));
     }
+    for (SparseTable& t : tabs) t.release();
   }
 
   FILE* fo = fopen(argv[2], "w");

@@ -85,6 +85,7 @@ EXPORTED = [
     "fts_idemix_cred_create", "fts_idemix_cred_destroy",
     "fts_idemix_identity_generate_batch", "fts_idemix_identity_generate_last_timings",
     "fts_debug_idemix_identity_draws", "fts_debug_idemix_identity_write",
+    "fts_debug_table_entries",
 ]
 # fts_idemix_identity_len, the one entry that returns a size_t, is bound below and not listed
 # here: this list is compared with the header's functions that return int, void or a string
@@ -225,6 +226,7 @@ def _load():
         "fts_issue_prove": ([P, U8P, S, S, C.POINTER(C.c_uint64), U8P, C.c_uint64, P, S, C.POINTER(S)], C.c_int),
         "fts_debug_rp_intermediates": ([P, S, P, P, P], C.c_int),
         "fts_debug_msm_stats": ([P, C.POINTER(C.c_int64)], C.c_int),
+        "fts_debug_table_entries": ([P, C.c_int, C.c_int, S, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), P], C.c_int),
         "fts_msm_g1": ([P, S, U8P, U8P, P], C.c_int),
         "fts_msm_stage": ([P, S, U8P, U8P, C.POINTER(P)], C.c_int),
         "fts_msm_stage_multiples": ([P, S, U8P, U8P, C.POINTER(P)], C.c_int),

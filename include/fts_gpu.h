@@ -336,6 +336,14 @@ int fts_last_timings_ex(const fts_ctx* ctx, const char** names, float* ms, doubl
  *  com_out: 64-byte com, hp_out: n x 64-byte H'_i); any pointer may be NULL */
 int fts_debug_rp_intermediates(fts_ctx* ctx, size_t i, uint8_t* ch_out, uint8_t* com_out, uint8_t* hp_out);
 
+/* debug: `count` entries T[w[j]][d[j] - 1] = d 2^(W w) B of one base's fixed-base table as
+ * the device holds them, out64: count x 64-byte X||Y BE.  wide = 0: the 16-bit set, bases
+ * [G_0.., H_0.., ped1, ped2, P, Q, K, ped0] (2n + 6); wide != 0: the set of
+ * fts_pp_info.wide_bits, bases [H_0.., K, P] (n + 2).  1 <= d <= 2^(W-1), w < ceil(255 / W);
+ * EINVAL otherwise, and on a host-only context */
+int fts_debug_table_entries(fts_ctx* ctx, int wide, int base, size_t count, const uint32_t* w, const uint32_t* d,
+                            uint8_t* out64);
+
 /* debug: bucket occupancy of the last RLC MSM: out[0] max bucket count, out[1] its index,
  * out[2] total buckets, out[3] non-empty buckets */
 int fts_debug_msm_stats(fts_ctx* ctx, int64_t* out);

@@ -7,8 +7,10 @@ at what the new formulas treat apart from the straight line: an accumulator that
 meets its own point again (doubling), its negative (identity, then more points),
 the identity as an input, a single non-zero digit (copy only), no non-zero digit.
 
-The wide (20/22-bit) tables are reachable only through proofs and stay covered by
-the byte-for-byte H' / com tests of test_gpu_rp.py and test_gpu_coalesce.py."""
+The wide (20/22-bit) tables see only hash outputs in the byte-for-byte H' / com tests
+of test_gpu_rp.py and test_gpu_coalesce.py; test_gpu_fixed_base.py sends chosen
+scalars through them (a proof's Delta), checks every width's recoding and products
+at the digit edges and reads the built tables back entry by entry."""
 import random
 
 import pytest
