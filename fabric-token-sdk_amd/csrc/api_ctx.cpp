@@ -520,6 +520,9 @@ const char* fts_status_str(int32_t s) {
     case FTS_E_AUDIT_RH_POINT: return "error while verifying the nym rh: invalid RhNym point";
     case FTS_E_AUDIT_RH_MISMATCH: return "error while verifying the nym rh: rh nym does not match";
     case FTS_E_SIGN_BADKEY: return "signing key out of range";
+    case FTS_E_CRED_MALFORMED: return "credential malformed";
+    case FTS_E_CRED_B: return "b-value from credential does not match the attribute values";
+    case FTS_E_CRED_PAIRING: return "credential is not cryptographically valid";
     default: return "unknown status";
   }
 }

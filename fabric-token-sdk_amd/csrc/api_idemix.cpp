@@ -1,8 +1,9 @@
 // C-ABI (include/fts_gpu.h): the idemix verifiers -- pseudonym signatures
-// (fts_idemix_ipk, idemix_kernels.hip) and the identities' association proofs
-// (fts_idemix_idv, idemix_identity_{bn,fbn}.hip).  Handles, slots and staging; the
-// untrusted bytes are parsed by host/idemix_parse.hpp, the kernels are reached
-// through device/launch.hpp.
+// (fts_idemix_ipk, idemix_kernels.hip), the identities' association proofs
+// (fts_idemix_idv, idemix_identity_{bn,fbn}.hip) and, on the same handle, credentials
+// (idemix_cred_{bn,fbn}.hip).  Handles, slots and staging; the untrusted bytes are parsed
+// by host/idemix_parse.hpp and host/identity_write.hpp, the kernels are reached through
+// device/launch.hpp.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -23,6 +24,7 @@
 #include "host/hip_owned.hpp"
 #include "host/host_pool.hpp"
 #include "host/idemix_parse.hpp"
+#include "host/identity_write.hpp"  // parse_credential
 #include "host/prover.hpp"  // Rng, RngSource: the signer's nonces
 #include "host/sign_encode.hpp"
 
@@ -58,7 +60,15 @@ struct IdvSlot {
   Event ev[3];
   float ms[2] = {0.f, 0.f};
   uint32_t stats[2] = {0u, 0u};
+  // credential calls take these slots too (one bound on the pairing stages in flight) and
+  // keep their figures apart from the identity calls'
+  float cred_ms[2] = {0.f, 0.f};
+  uint32_t cred_stats[2] = {0u, 0u};
 };
+// credentials per kernel sequence of fts_idemix_cred_verify_batch: bounds what a call asks a
+// slot for (2.5 KB of device memory per credential, 42 MB) and still puts 1,792 waves on
+// the device in k_cred_var
+constexpr size_t CRV_TILE = 16384;
 
 constexpr int AUD_NSLOT = 3;  // audit-match calls in flight per handle, beside the identity slots
 struct AuditSlot {
@@ -129,6 +139,9 @@ struct fts_idemix_idv {
   // and pre-round-6 path); last call's groups and identities paired one by one
   bool batch = true;
   uint32_t last_stats[2] = {0u, 0u};
+  // the last credential batch (fts_idemix_cred_verify_batch), under the ring's lock
+  float last_cred_ms[2] = {0.f, 0.f};
+  uint32_t last_cred_stats[2] = {0u, 0u};
   // BN254 epoch keys already subgroup-checked by this context (128 raw bytes ->
   // verdict): an honest stream carries one key per epoch, and k_idv_g2_check is
   // one 254-step G2 chain on one lane (7.7 ms, on the call's critical path)
@@ -692,6 +705,129 @@ int fts_idemix_identity_last_stats(fts_idemix_idv* K, uint32_t* out) {
   if (!K || !out) return FTS_API_EINVAL;
   std::lock_guard<std::mutex> l(K->ring.mu);
   out[0] = K->last_stats[0], out[1] = K->last_stats[1];
+  return FTS_API_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Credentials (Credential.Ver, pairing equation included)
+// ---------------------------------------------------------------------------
+int fts_idemix_cred_verify_batch(fts_idemix_idv* K, size_t n, const fts_idemix_cred_item* items, int32_t* status) {
+  if (!K || n > (size_t)(1u << 22) || (n && (!items || !status))) return FTS_API_EINVAL;
+  if (n == 0) return FTS_API_OK;
+  const bool bn = K->curve == FTS_CURVE_BN254;
+  const uint32_t* const rmod = bn ? u256::kRbn : u256::kRfbn;
+  // a slot of the identity ring: identity and credential calls share the bound on pairing
+  // stages in flight (IDV_NSLOT)
+  auto guard = K->ring.acquire([K](IdvSlot& S) {
+    K->last_cred_ms[0] = S.cred_ms[0], K->last_cred_ms[1] = S.cred_ms[1];
+    K->last_cred_stats[0] = S.cred_stats[0], K->last_cred_stats[1] = S.cred_stats[1];
+  });
+  IdvSlot& D = guard.slot();
+  ICHK(hipSetDevice(K->device));
+  const size_t T = std::min(n, CRV_TILE);
+  auto al = [](size_t x) { return (x + 255) & ~size_t(255); };
+  // staged (host + device): rec | pts | status; host only: the batch check's list length,
+  // read back; device only: zk | pin | scratch
+  const size_t rec_b = T * CRV_REC_WORDS * 4;
+  const size_t o_pts = al(rec_b), o_st = al(o_pts + T * CRV_PTS_BYTES), o_cnt = al(o_st + T * 4), h_need = o_cnt + 256;
+  const size_t o_zk = h_need, o_pin = al(o_zk + T * 4), o_scr = al(o_pin + T * 32 * 4);
+  const size_t scr_w = std::max(cred_scratch_words(T), bp_scratch_words(T));
+  const size_t d_need = o_scr + scr_w * 4;
+  if (D.h_buf.cap < h_need && !D.h_buf.reserve(h_need)) return FTS_API_ENOMEM;
+  if (D.d_buf.cap < d_need && !D.d_buf.reserve(d_need)) return FTS_API_ENOMEM;
+  uint8_t* h = D.h_buf.as<uint8_t>();
+  uint8_t* d = D.d_buf.as<uint8_t>();
+  // sk (with E, S and the attributes) staged on the host and the device, then HSk sk, the
+  // lane tables and the pairing inputs: wiped on every way out
+  SecretWipe wipe_rec(D.stream), wipe_scr(D.stream);
+  wipe_rec.host = h, wipe_rec.dev = d, wipe_rec.bytes = rec_b;
+  wipe_scr.dev = d + o_pin, wipe_scr.bytes = d_need - o_pin;
+  uint32_t* scr = reinterpret_cast<uint32_t*>(d + o_scr);
+  CredChain cc;
+  cc.s = D.stream, cc.rec = reinterpret_cast<const uint32_t*>(d), cc.pts = d + o_pts, cc.scr = scr;
+  cc.pin = reinterpret_cast<uint32_t*>(d + o_pin), cc.zk = reinterpret_cast<int32_t*>(d + o_zk);
+  cc.st = reinterpret_cast<int32_t*>(d + o_st), cc.tables = K->d_tables.as<uint32_t>();
+  // the pairing stage of the identity verifier, on (A, E A - B) instead of (A', -ABar)
+  Chain c{};
+  c.s = D.stream, c.scr = scr, c.pin = cc.pin, c.zk = cc.zk, c.st = cc.st, c.lines = K->d_lines.as<uint32_t>();
+  float ms[2] = {0.f, 0.f};
+  uint32_t stats[2] = {0u, 0u};
+  const size_t CH = 512;
+  for (size_t base = 0; base < n; base += T) {
+    const size_t m = std::min(T, n - base), nch = (m + CH - 1) / CH, ng = (m + BP_G - 1) / BP_G;
+    host_parallel_for(nch, [&](size_t ch) {
+      struct Parsed {
+        idgen::CredFields f;
+        ~Parsed() {
+          volatile uint8_t* p = reinterpret_cast<volatile uint8_t*>(this);
+          for (size_t q = 0; q < sizeof(Parsed); q++) p[q] = 0;
+        }
+      } pc;
+      for (size_t j = ch * CH; j < std::min(m, (ch + 1) * CH); j++) {
+        const fts_idemix_cred_item& it = items[base + j];
+        uint32_t* R = reinterpret_cast<uint32_t*>(h) + j * CRV_REC_WORDS;  // E S sk attrs[0..3]
+        uint8_t* P = h + o_pts + j * CRV_PTS_BYTES;
+        const bool good = it.cred && it.cred_len && it.sk32 && idgen::parse_credential(it.cred, it.cred_len, bn, pc.f) &&
+                          u256::be_limbs(it.sk32, 32, R + 16) && !u256::ge(R + 16, rmod);
+        if (good) {
+          memcpy(R, pc.f.e, 32), memcpy(R + 8, pc.f.s, 32), memcpy(R + 24, pc.f.attrs, 128);
+          memcpy(P, pc.f.a, 64), memcpy(P + 64, pc.f.b, 64);
+        } else {
+          memset(R, 0, CRV_REC_WORDS * 4), memset(P, 0, CRV_PTS_BYTES);
+        }
+        reinterpret_cast<int32_t*>(h + o_st)[j] = good ? FTS_OK : FTS_E_CRED_MALFORMED;
+      }
+    });
+    cc.n = c.n = (int)m;
+    c.gok = reinterpret_cast<int32_t*>(scr + bp_gok_off(m, ng));
+    c.cnt = reinterpret_cast<int32_t*>(scr + bp_cnt_off(m, ng));
+    c.list = reinterpret_cast<int32_t*>(scr + bp_list_off(m, ng));
+    if (K->batch && getrandom(c.key.k, sizeof c.key.k, 0) != (ssize_t)sizeof c.key.k) return FTS_API_EDEVICE;
+    ICHK(hipMemcpyAsync(d, h, o_st + m * 4, hipMemcpyHostToDevice, D.stream));
+    ICHK(hipEventRecord(D.ev[0], D.stream));
+    bn ? launch_cred_prep<BnCurve>(cc) : launch_cred_prep<FbnCurve>(cc);
+    ICHK(hipEventRecord(D.ev[1], D.stream));
+    unsigned nlist = 0;
+    if (K->batch) {
+      bn ? launch_batch<BnCurve>(c) : launch_batch<FbnCurve>(c);
+      ICHK(hipMemcpyAsync(h + o_cnt, c.cnt, 4, hipMemcpyDeviceToHost, D.stream));
+      ICHK(hipStreamSynchronize(D.stream));
+      nlist = *reinterpret_cast<const uint32_t*>(h + o_cnt);
+      if (nlist > m) return FTS_API_EDEVICE;
+      if (nlist) bn ? launch_pairing<BnCurve>(c, nlist, true) : launch_pairing<FbnCurve>(c, nlist, true);
+    } else {
+      bn ? launch_pairing<BnCurve>(c, (unsigned)m, false) : launch_pairing<FbnCurve>(c, (unsigned)m, false);
+    }
+    ICHK(hipGetLastError());
+    ICHK(hipEventRecord(D.ev[2], D.stream));
+    ICHK(hipMemcpyAsync(h + o_st, d + o_st, m * 4, hipMemcpyDeviceToHost, D.stream));
+    ICHK(hipStreamSynchronize(D.stream));
+    // the pairing kernels write the identity verifier's verdict
+    const int32_t* hst = reinterpret_cast<const int32_t*>(h + o_st);
+    for (size_t j = 0; j < m; j++) status[base + j] = hst[j] == FTS_E_ID_PAIRING ? FTS_E_CRED_PAIRING : hst[j];
+    float a = 0.f, b = 0.f;
+    ICHK(hipEventElapsedTime(&a, D.ev[0], D.ev[1]));
+    ICHK(hipEventElapsedTime(&b, D.ev[1], D.ev[2]));
+    ms[0] += a, ms[1] += b;
+    stats[0] += K->batch ? (uint32_t)ng : 0u;
+    stats[1] += K->batch ? nlist : (uint32_t)m;
+  }
+  D.cred_ms[0] = ms[0], D.cred_ms[1] = ms[1];
+  D.cred_stats[0] = stats[0], D.cred_stats[1] = stats[1];
+  return FTS_API_OK;
+}
+
+int fts_idemix_cred_verify_last_timings(fts_idemix_idv* K, float* ms2) {
+  if (!K || !ms2) return FTS_API_EINVAL;
+  std::lock_guard<std::mutex> l(K->ring.mu);
+  ms2[0] = K->last_cred_ms[0], ms2[1] = K->last_cred_ms[1];
+  return FTS_API_OK;
+}
+
+int fts_idemix_cred_verify_last_stats(fts_idemix_idv* K, uint32_t* out2) {
+  if (!K || !out2) return FTS_API_EINVAL;
+  std::lock_guard<std::mutex> l(K->ring.mu);
+  out2[0] = K->last_cred_stats[0], out2[1] = K->last_cred_stats[1];
   return FTS_API_OK;
 }
 

@@ -211,4 +211,21 @@ void launch_idgen_cred(const uint32_t* tables, const uint32_t* ab, const uint32_
                        hipStream_t s);
 template <class CV>
 hipError_t launch_idgen(const GenChain& c);
+
+// ---- idemix_cred_<cv>.hip (device/cred_kernels.hpp): credential verification up to the
+// pairing stage's inputs (launch_batch / launch_pairing above then run on pin, zk and st)
+// per credential: E S sk attrs[0..3] as canonical limbs; A then B, X || Y raw
+constexpr int CRV_NPROD = 7, CRV_REC_WORDS = CRV_NPROD * 8, CRV_PTS_BYTES = 2 * 64;
+struct CredChain {
+  hipStream_t s;
+  int n;
+  const uint32_t* rec;  // [n][CRV_REC_WORDS]
+  const uint8_t* pts;   // [n][CRV_PTS_BYTES]
+  uint32_t *scr, *pin;  // cred_scratch_words(n); [n][32]
+  int32_t *zk, *st;
+  const uint32_t* tables;  // the issuer's seven
+};
+template <class CV>
+void launch_cred_prep(const CredChain& c);
+size_t cred_scratch_words(size_t n);
 }  // namespace idv

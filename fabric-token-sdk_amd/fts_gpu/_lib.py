@@ -47,6 +47,9 @@ FTS_E_AUDIT_NO_RHNYM = 31
 FTS_E_AUDIT_RH_POINT = 32
 FTS_E_AUDIT_RH_MISMATCH = 33
 FTS_E_SIGN_BADKEY = 34
+FTS_E_CRED_MALFORMED = 36  # 35 stays unassigned ("unknown status")
+FTS_E_CRED_B = 37
+FTS_E_CRED_PAIRING = 38
 # signing (include/fts_gpu.h)
 FTS_ECDSA_SIG_MAX = 72
 FTS_NYM_SIG_LEN = 136
@@ -86,6 +89,7 @@ EXPORTED = [
     "fts_idemix_identity_generate_batch", "fts_idemix_identity_generate_last_timings",
     "fts_debug_idemix_identity_draws", "fts_debug_idemix_identity_write",
     "fts_debug_table_entries",
+    "fts_idemix_cred_verify_batch", "fts_idemix_cred_verify_last_timings", "fts_idemix_cred_verify_last_stats",
 ]
 # fts_idemix_identity_len, the one entry that returns a size_t, is bound below and not listed
 # here: this list is compared with the header's functions that return int, void or a string
@@ -150,6 +154,10 @@ class NymItem(C.Structure):
 class AuditItem(C.Structure):
     _fields_ = [("id", C.c_void_p), ("id_len", C.c_size_t), ("eid", C.c_void_p), ("eid_len", C.c_size_t),
                 ("r_eid32", C.c_void_p), ("rh", C.c_void_p), ("rh_len", C.c_size_t), ("r_rh32", C.c_void_p)]
+
+
+class CredItem(C.Structure):
+    _fields_ = [("cred", C.c_void_p), ("cred_len", C.c_size_t), ("sk32", C.c_void_p)]
 
 
 class ActionWitness(C.Structure):
@@ -266,6 +274,9 @@ def _load():
         "fts_idemix_pairing_debug": ([P, C.c_int, U8P, C.c_int, C.POINTER(C.c_uint32)], C.c_int),
         "fts_idemix_audit_match_batch": ([P, S, C.POINTER(AuditItem), I32P], C.c_int),
         "fts_idemix_audit_last_timings": ([P, C.POINTER(C.c_float)], C.c_int),
+        "fts_idemix_cred_verify_batch": ([P, S, C.POINTER(CredItem), I32P], C.c_int),
+        "fts_idemix_cred_verify_last_timings": ([P, C.POINTER(C.c_float)], C.c_int),
+        "fts_idemix_cred_verify_last_stats": ([P, C.POINTER(C.c_uint32)], C.c_int),
         "fts_token_commit_batch_gpu": ([P, S, C.POINTER(CommitItem), P], C.c_int),
         "fts_token_commit_batch_width": ([], C.c_int),
         "fts_transfer_generate": ([P, C.POINTER(GenAction), C.c_uint64, C.POINTER(GenResult)], C.c_int),

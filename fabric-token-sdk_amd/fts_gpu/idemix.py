@@ -15,7 +15,9 @@ protos that the verifiers above accept (k_nym_sign / k_nym_sign_fbn).
 
 Identities: ``IdentityVerifier`` checks owner identities and matches audit info against
 them; ``Credential(verifier, cred, sk).generate(n)`` produces them on the device
-(KeyManager.Identity, services/identity/idemix/km.go:173-290).
+(KeyManager.Identity, services/identity/idemix/km.go:173-290);
+``IdentityVerifier.verify_credentials(creds, sks)`` / ``VerifyCredential(cred, sk)`` check
+credentials as NewKeyManager does, pairing equation included (km.go:117-133).
 
 The issuer key is the idemix IssuerPublicKey proto a zkatdlog PublicParams
 carries, on BN254 (the tokengen key of zkatdlog_pp.json) or FP256BN_AMCL (the
@@ -34,6 +36,7 @@ from ._lib import (FTS_E_AUDIT_MALFORMED, FTS_E_AUDIT_NO_EIDNYM, FTS_E_AUDIT_EID
                    FTS_E_AUDIT_EID_MISMATCH, FTS_E_AUDIT_NO_RHNYM, FTS_E_AUDIT_RH_POINT, FTS_E_AUDIT_RH_MISMATCH)
 from ._lib import FTS_CURVE_BN254, FTS_CURVE_FP256BN_AMCL  # noqa: F401
 from ._lib import FTS_E_SIGN_BADKEY, FTS_NYM_SIG_LEN  # noqa: F401
+from ._lib import FTS_E_CRED_MALFORMED, FTS_E_CRED_B, FTS_E_CRED_PAIRING  # noqa: F401
 from ._lib import FTS_SEED_OS_RANDOM as OS_RANDOM
 
 
@@ -319,6 +322,58 @@ class IdentityVerifier:
         ms = C.c_float()
         L.check("fts_idemix_audit_last_timings", L.lib.fts_idemix_audit_last_timings(self.h, C.byref(ms)))
         return ms.value
+
+    def verify_credentials(self, creds, sks):
+        """Credential.Ver under the handle's issuer key, pairing equation included, for n
+        (Credential proto, user secret) pairs in one device pass (fts_idemix_cred_verify_batch;
+        services/identity/idemix/km.go:117-133).  sks: ints or 32 big-endian bytes; None for
+        either input is a NULL pointer.  -> int32 status array (FTS_OK or FTS_E_CRED_*)"""
+        n = len(creds)
+        if len(sks) != n:
+            raise ValueError("creds and sks must have the same length")
+        st = np.zeros(n, dtype=np.int32)
+        if n == 0:
+            return st
+
+        def z32(v):
+            if v is None:
+                return None
+            if isinstance(v, int):
+                return v.to_bytes(32, "big") if 0 <= v < (1 << 256) else b"\xff" * 32
+            v = bytes(v)
+            if len(v) != 32:
+                raise ValueError("the user secret is an int or 32 big-endian bytes")
+            return v
+
+        def ptr(b):  # None: NULL; b"" keeps a valid pointer
+            return None if b is None else C.cast(C.c_char_p(b), C.c_void_p)
+        keep = [(None if c is None else bytes(c), z32(s)) for c, s in zip(creds, sks)]
+        items = (L.CredItem * n)()
+        for i, (c, s) in enumerate(keep):
+            items[i].cred, items[i].cred_len, items[i].sk32 = ptr(c), len(c or b""), ptr(s)
+        L.check("fts_idemix_cred_verify_batch",
+                L.lib.fts_idemix_cred_verify_batch(self.h, n, items, st.ctypes.data_as(C.POINTER(C.c_int32))))
+        return st
+
+    def VerifyCredential(self, cred, sk):
+        """raises IdentityError with the reference's message, as NewKeyManager does for a
+        signer config whose credential does not verify"""
+        st = int(self.verify_credentials([cred], [sk])[0])
+        if st != FTS_OK:
+            raise IdentityError(message(st), st)
+
+    def last_cred_kernel_ms(self):
+        """(decode + products + B check, pairing stage) HIP-event ms of the last credential batch"""
+        ms = (C.c_float * 2)()
+        L.check("fts_idemix_cred_verify_last_timings", L.lib.fts_idemix_cred_verify_last_timings(self.h, ms))
+        return float(ms[0]), float(ms[1])
+
+    def last_cred_stats(self):
+        """(groups checked with one randomised pairing product, credentials paired one by
+        one) of the last credential batch; (0, n) with FTS_IDV_BATCH=0"""
+        out = (C.c_uint32 * 2)()
+        L.check("fts_idemix_cred_verify_last_stats", L.lib.fts_idemix_cred_verify_last_stats(self.h, out))
+        return int(out[0]), int(out[1])
 
     def pairing_debug(self, which, p64, final_exp=True):
         """e(W or g2, P) on the handle's curve, P = X || Y (64 raw BE bytes): 6 Fp2

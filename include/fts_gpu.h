@@ -91,7 +91,14 @@ enum fts_status {
   FTS_E_AUDIT_RH_MISMATCH = 33,  /* "rh nym does not match" */
   /* signing (fts_ecdsa_sign_batch, fts_nym_sign_batch): no reference string, a signer holding
    * such a key cannot exist there */
-  FTS_E_SIGN_BADKEY = 34         /* private scalar out of range: ECDSA d = 0 or d >= n; nym sk or rnym >= r */
+  FTS_E_SIGN_BADKEY = 34,        /* private scalar out of range: ECDSA d = 0 or d >= n; nym sk or rnym >= r */
+  /* idemix credential validity (services/identity/idemix/km.go:117-133 -> IBM/idemix Credential.Ver),
+   * in the order checked.  35 stays unassigned: fts_status_str(35) is "unknown status", which callers
+   * have been able to rely on as the first code past the table */
+  FTS_E_CRED_MALFORMED = 36,     /* NULL or empty input, Credential proto does not parse, attributes other
+                                    than four, a scalar >= r, A or B off the curve or the identity */
+  FTS_E_CRED_B = 37,             /* "b-value from credential does not match the attribute values" */
+  FTS_E_CRED_PAIRING = 38        /* "credential is not cryptographically valid" */
 };
 
 /* ---- API return codes ---- */
@@ -774,8 +781,10 @@ int fts_idemix_audit_last_timings(fts_idemix_idv* idv, float* ms);
  * sk, E, S and the attributes below r; B = g1 + HRand S + HSk sk + sum HAttrs[i] attrs[i]
  * (Credential.Ver's B check); a CRI that does not parse, lacks its epoch key or names a
  * revocation algorithm other than ALG_NO_REVOCATION.  FTS_API_EINVAL for a NULL argument.
- * NOT checked: the credential's pairing equation e(W + g2 E, A) = e(g2, B), which needs a
- * scalar product in G2 -- a forged A only yields identities that the verifier rejects.
+ * NOT checked here: the credential's pairing equation e(W + g2 E, A) = e(g2, B).  By
+ * bilinearity it is e(W, A) e(g2, E A - B) = 1, which fts_idemix_cred_verify_batch checks
+ * on the verifier's handle; without that call a forged A only yields identities that the
+ * verifier rejects.
  * Secrets the handle holds on the device are zeroed before they are freed, on destroy and on
  * every error path of create.  Not hardened against timing or cache side channels (table
  * indices and branches depend on secrets), as the other signers. */
@@ -823,6 +832,48 @@ int fts_debug_idemix_identity_draws(int curve_id, uint64_t seed, uint64_t i, uin
 int fts_debug_idemix_identity_write(int curve_id, const uint8_t* pts6x64, const uint8_t* sc13x32,
                                     const uint8_t* nonce32, const uint8_t* epoch_pk128, uint64_t epoch, uint8_t* out,
                                     size_t out_cap, size_t* out_len);
+
+/* ---- idemix credentials verified on the device ----
+ * Replaces the check KeyManager construction makes of a signer config
+ * (services/identity/idemix/km.go:117-133: Csp.Verify(userKey, cred, ..., IdemixCredentialSignerOpts)
+ * -> IBM/idemix Credential.Ver), pairing equation included, for n credentials under the handle's
+ * issuer key.  cred: the idemix Credential proto (IdemixSignerConfig.Cred); sk32: the user
+ * secret, 32 B big-endian -- the inputs of fts_idemix_cred_create.
+ * status[i] <- FTS_OK or the first failing check:
+ *   FTS_E_CRED_MALFORMED  a NULL cred or sk32; an empty proto or one that does not parse;
+ *                         attributes other than four; E, S, an attribute or sk >= r; A or B that
+ *                         does not decode on the handle's curve (BN254: flag bits clear, canonical
+ *                         coordinates, on the curve; FP256BN_AMCL: coordinates below p, on the
+ *                         curve) or is the identity
+ *   FTS_E_CRED_B          B != g1 + HRand S + HSk sk + sum HAttrs[i] attrs[i]
+ *   FTS_E_CRED_PAIRING    e(W + g2 E, A) != e(g2, B), checked as e(W, A) e(g2, E A - B) = 1:
+ *                         the shape of the identity verifier's equation, on the same Miller-loop
+ *                         lines, per group of 256 credentials as one randomised product (fresh
+ *                         getrandom weights per call, soundness 2^-128; G1 has cofactor 1 on both
+ *                         curves, so every decoded point has order r); the credentials of a
+ *                         failing group are paired one by one (all of them with FTS_IDV_BATCH=0)
+ * CRI and revocation are not looked at.  FTS_API_EINVAL for a NULL handle, NULL arrays with
+ * n > 0 or n > 2^22; n = 0 is FTS_API_OK; FTS_API_EDEVICE for a device failure or a failure of
+ * getrandom; FTS_API_ENOMEM.  Thread-safe: a call takes one of the handle's 8 identity-
+ * verification slots, so identity and credential calls together never have more than 8
+ * pairing stages in flight on a handle.  A call above 16,384 credentials runs in tiles of that
+ * size, so it asks a slot for at most 42 MB of device memory.  sk, HSk sk and the lane tables
+ * of E A are wiped from the slot's host and device buffers on every way out.  Not hardened
+ * against timing or cache side channels, as the signers. */
+typedef struct {
+  const uint8_t* cred;
+  size_t cred_len;
+  const uint8_t* sk32;
+} fts_idemix_cred_item;
+int fts_idemix_cred_verify_batch(fts_idemix_idv* idv, size_t n, const fts_idemix_cred_item* items, int32_t* status);
+/* HIP-event durations (ms) of the last credential batch, summed over its tiles: [0] the prep
+ * kernels (decode, the seven products, the B check and E A - B), [1] the pairing stage.
+ * fts_idemix_identity_last_timings keeps reporting the last identity batch. */
+int fts_idemix_cred_verify_last_timings(fts_idemix_idv* idv, float* ms2);
+/* The last credential batch's pairing check, summed over its tiles: out2[0] = groups checked
+ * with one randomised pairing product each (0 with FTS_IDV_BATCH=0), out2[1] = credentials
+ * paired one by one. */
+int fts_idemix_cred_verify_last_stats(fts_idemix_idv* idv, uint32_t* out2);
 
 #ifdef __cplusplus
 }
