@@ -244,14 +244,13 @@ int fts_idemix_identity_nym(const uint8_t* id, size_t len, const uint8_t** nym, 
 int fts_nym_verify_batch(fts_idemix_ipk* K, size_t n, const fts_nym_item* items, int32_t* status) {
   if (!K || n > (size_t)(1u << 24) || (n && (!items || !status))) return FTS_API_EINVAL;
   if (n == 0) return FTS_API_OK;
-  // message words per item: BN254 the message alone; FP256BN the whole hashed
-  // stream (166-byte prefix + message), each padded to whole words + 1
+  // message words per item (nym_stream_words): BN254 the message alone; FP256BN the
+  // whole hashed stream
   const bool bn = K->curve == FTS_CURVE_BN254;
-  const size_t pre = bn ? 0 : 166;
   size_t mtot_w = 0;
   for (size_t i = 0; i < n; i++) {
     if (items[i].msg_len > 0xffffff00u || (items[i].msg_len && !items[i].msg)) return FTS_API_EINVAL;
-    mtot_w += (pre + items[i].msg_len + 3) / 4 + 1;
+    mtot_w += nym_stream_words(bn, items[i].msg_len);
   }
   auto guard = K->ring.acquire([K](NymSlot& S) { K->last_ms = S.ms; });
   NymSlot& D = guard.slot();
@@ -272,33 +271,17 @@ int fts_nym_verify_batch(fts_idemix_ipk* K, size_t n, const fts_nym_item* items,
   uint64_t* hoff = reinterpret_cast<uint64_t*>(h + o_off);
   {
     uint64_t o = 0;
-    for (size_t i = 0; i < n; i++) hoff[i] = o, o += (pre + items[i].msg_len + 3) / 4 + 1;
+    for (size_t i = 0; i < n; i++) hoff[i] = o, o += nym_stream_words(bn, items[i].msg_len);
   }
   auto pack = [&](size_t lo, size_t hi) {
     for (size_t i = lo; i < hi; i++) {
       const fts_nym_item& it = items[i];
       int32_t st = parse_nym_sig(it.sig, it.sig_len, bn, reinterpret_cast<uint32_t*>(h) + i * NREC);
-      uint8_t* nr = h + o_nym + i * 64;
-      // NymPublicKey import (crypto/deserializer.go:49-56) precedes Verify: a key of
-      // the wrong length / form fails first; its point checks run on the device.
-      // BN254: G1.Bytes() raw X||Y (64 B); FP256BN: ECP.ToBytes 0x04||X||Y (65 B).
-      const bool key_ok = it.nym && (bn ? it.nym_len == 64 : it.nym_len == 65 && it.nym[0] == 0x04);
-      if (key_ok) memcpy(nr, it.nym + (bn ? 0 : 1), 64);
-      else memset(nr, 0, 64), st = FTS_E_NYM_BADKEY;
+      // NymPublicKey import precedes Verify: a key of the wrong length / form fails first
+      if (!pack_nym_item(bn, it.nym, it.nym_len, K->hash, it.msg, it.msg_len, h + o_nym + i * 64,
+                         h + o_msg + hoff[i] * 4, reinterpret_cast<uint32_t*>(h + o_len) + i))
+        st = FTS_E_NYM_BADKEY;
       reinterpret_cast<int32_t*>(h + o_st)[i] = st;
-      reinterpret_cast<uint32_t*>(h + o_len)[i] = (uint32_t)(pre + it.msg_len);
-      uint8_t* mw = h + o_msg + hoff[i] * 4;
-      const size_t wl = ((pre + it.msg_len + 3) / 4 + 1) * 4;
-      if (!bn) {  // "sign" || 0x04 || t (device) || Nym || ipk.Hash
-        memcpy(mw, "sign", 4);
-        mw[4] = 0x04;
-        memset(mw + 5, 0, 64);
-        if (key_ok) memcpy(mw + 69, it.nym, 65);
-        else memset(mw + 69, 0, 65);
-        memcpy(mw + 134, K->hash, 32);
-      }
-      if (it.msg_len) memcpy(mw + pre, it.msg, it.msg_len);
-      memset(mw + pre + it.msg_len, 0, wl - pre - it.msg_len);
     }
   };
   const size_t CH = 2048, nch = (n + CH - 1) / CH;
@@ -334,11 +317,10 @@ int fts_nym_sign_batch(fts_idemix_ipk* K, size_t n, const fts_nym_sign_item* ite
   if (n == 0) return FTS_API_OK;
   const bool bn = K->curve == FTS_CURVE_BN254;
   const uint32_t* const rmod = bn ? u256::kRbn : u256::kRfbn;
-  const size_t pre = bn ? 0 : 166;  // the hashed stream, laid out as for fts_nym_verify_batch
-  size_t mtot_w = 0;
+  size_t mtot_w = 0;  // the hashed stream, laid out as for fts_nym_verify_batch
   for (size_t i = 0; i < n; i++) {
     if (items[i].msg_len > 0xffffff00u || (items[i].msg_len && !items[i].msg)) return FTS_API_EINVAL;
-    mtot_w += (pre + items[i].msg_len + 3) / 4 + 1;
+    mtot_w += nym_stream_words(bn, items[i].msg_len);
   }
   const host::RngSource src(seed);
   if (!src.ok) return FTS_API_EDEVICE;
@@ -358,7 +340,7 @@ int fts_nym_sign_batch(fts_idemix_ipk* K, size_t n, const fts_nym_sign_item* ite
   uint64_t* hoff = reinterpret_cast<uint64_t*>(h + o_off);
   {
     uint64_t o = 0;
-    for (size_t i = 0; i < n; i++) hoff[i] = o, o += (pre + items[i].msg_len + 3) / 4 + 1;
+    for (size_t i = 0; i < n; i++) hoff[i] = o, o += nym_stream_words(bn, items[i].msg_len);
   }
   // uniform below r by rejection: Rng::fr() on BN254, the same construction over the
   // 256-bit r of FP256BN (four words, no mask)
@@ -383,10 +365,8 @@ int fts_nym_sign_batch(fts_idemix_ipk* K, size_t n, const fts_nym_sign_item* ite
       if (!it.sk32 || !it.rnym32 || !u256::be_limbs(it.sk32, 32, R) || !u256::be_limbs(it.rnym32, 32, R + 8) ||
           u256::ge(R, rmod) || u256::ge(R + 8, rmod))
         st = FTS_E_SIGN_BADKEY;
-      uint8_t* nr = h + o_nym + i * 64;
-      const bool key_ok = it.nym && (bn ? it.nym_len == 64 : it.nym_len == 65 && it.nym[0] == 0x04);
-      if (key_ok) memcpy(nr, it.nym + (bn ? 0 : 1), 64);
-      else memset(nr, 0, 64);
+      const bool key_ok = pack_nym_item(bn, it.nym, it.nym_len, K->hash, it.msg, it.msg_len, h + o_nym + i * 64,
+                                        h + o_msg + hoff[i] * 4, reinterpret_cast<uint32_t*>(h + o_len) + i);
       if (st == FTS_OK && !key_ok) st = FTS_E_NYM_BADKEY;
       if (st == FTS_OK) {
         host::Rng rng = src.at(i);
@@ -399,19 +379,6 @@ int fts_nym_sign_batch(fts_idemix_ipk* K, size_t n, const fts_nym_sign_item* ite
         memset(R, 0, NSREC * 4);
       }
       reinterpret_cast<int32_t*>(h + o_st)[i] = st;
-      reinterpret_cast<uint32_t*>(h + o_len)[i] = (uint32_t)(pre + it.msg_len);
-      uint8_t* mw = h + o_msg + hoff[i] * 4;
-      const size_t wl = ((pre + it.msg_len + 3) / 4 + 1) * 4;
-      if (!bn) {  // "sign" || 0x04 || t (device) || Nym || ipk.Hash
-        memcpy(mw, "sign", 4);
-        mw[4] = 0x04;
-        memset(mw + 5, 0, 64);
-        if (key_ok) memcpy(mw + 69, it.nym, 65);
-        else memset(mw + 69, 0, 65);
-        memcpy(mw + 134, K->hash, 32);
-      }
-      if (it.msg_len) memcpy(mw + pre, it.msg, it.msg_len);
-      memset(mw + pre + it.msg_len, 0, wl - pre - it.msg_len);
     }
   });
   wipe.dev = d;

@@ -28,63 +28,14 @@
 //                 products): no Jacobian + Jacobian addition and 11, not 19, points of
 //                 scratch per identity
 //   k_idg_finish  lane per identity: the 11 transcript points to affine with one inversion
-//                 (Montgomery's trick), the Fiat-Shamir transcript of k_idv_tvals (restated
-//                 here, so the verify kernels stay as they were), c, the 12 responses;
+//                 (Montgomery's trick), the Fiat-Shamir transcript of k_idv_tvals (hashed by
+//                 the same sink_digest and nonce_challenge), c, the 12 responses;
 //                 six points and thirteen scalars (c and the responses) out, in wire byte order
 // Not hardened against timing side channels (table indices and branches depend on secrets).
 #pragma once
 #include "idv_kernels.hpp"
 
 namespace idv {
-
-// ------------------------------------------------------------- Fr per curve
-// Values are canonical LE limbs; `m` marks a Montgomery-form factor: mul(m, plain) is plain.
-template <class CV>
-struct Zr;
-template <>
-struct Zr<BnCurve> {
-  using Z = Fr;
-  static FTS_DEV Z ld(const uint32_t* p) {
-    Z r;
-#pragma unroll
-    for (int k = 0; k < 8; k++) r.v[k] = p[k];
-    return r;
-  }
-  static FTS_DEV Z add(const Z& a, const Z& b) { return f_add(a, b); }
-  static FTS_DEV Z sub(const Z& a, const Z& b) { return f_sub(a, b); }
-  static FTS_DEV Z neg(const Z& a) { return f_neg(a); }
-  static FTS_DEV Z mul(const Z& a, const Z& b) { return f_mul(a, b); }
-  static FTS_DEV Z to_mont(const Z& a) { return f_to_mont(a); }
-  static FTS_DEV Z from_mont(const Z& a) { return f_from_mont(a); }
-  static FTS_DEV Z inv_m(const Z& am) { return f_inv(am); }  // Montgomery in and out
-};
-template <>
-struct Zr<FbnCurve> {
-  using Z = p256::F<fbn::RM>;
-  static FTS_DEV Z ld(const uint32_t* p) { return p256::load<fbn::RM>(p); }
-  static FTS_DEV Z add(const Z& a, const Z& b) { return p256::add(a, b); }
-  static FTS_DEV Z sub(const Z& a, const Z& b) { return p256::sub(a, b); }
-  static FTS_DEV Z neg(const Z& a) {
-    Z z;
-#pragma unroll
-    for (int k = 0; k < 8; k++) z.v[k] = 0u;
-    return p256::sub(z, a);
-  }
-  static FTS_DEV Z mul(const Z& a, const Z& b) { return p256::mul(a, b); }
-  static FTS_DEV Z to_mont(const Z& a) { return p256::to_mont(a); }
-  static FTS_DEV Z from_mont(const Z& a) { return p256::from_mont(a); }
-  // a^(r - 2), Montgomery in and out (r's top bit is set; r - 2 borrows nothing past limb 0)
-  static FTS_DEV Z inv_m(const Z& am) {
-    Z r = am;
-#pragma unroll 1
-    for (int bit = 254; bit >= 0; bit--) {
-      r = p256::mul(r, r);
-      const uint32_t e = bit < 32 ? fbn::RM::M[0] - 2u : fbn::RM::M[bit >> 5];
-      if ((e >> (bit & 31)) & 1u) r = p256::mul(r, am);
-    }
-    return r;
-  }
-};
 
 // affine Montgomery point (identity: zeros) -> X || Y as 16 big-endian words (the bytes of
 // G1.Bytes() after the curve's prefix; AMCL writes infinity as 0 || 1)
@@ -281,6 +232,7 @@ __global__ void __launch_bounds__(256) k_idg_finish(int n, const uint32_t* __res
     uint32_t pw[16];
     point_be_words<CV>(get_f<CV>(P, 0), get_f<CV>(P, 8), pw);
     if (CV::G1_BYTES == 65) M.put_byte(0x04);
+#pragma unroll  // said, not left to the heuristic: rolled, the FP256BN kernel takes 98 registers for 86
     for (int k = 0; k < 16; k++) M.put_word(pw[k]);
     const int o = IDG_Q_OUT[q];
     if (o >= 0)
@@ -288,36 +240,13 @@ __global__ void __launch_bounds__(256) k_idg_finish(int n, const uint32_t* __res
   }
   for (int k = 0; k < 8; k++) M.put_word(ipk_hash[k]);
   M.put_word(0u);  // Disclosure: four hidden attributes
-  const uint32_t len = M.off;
-  const uint32_t nb = sha_blocks(len);
-  M.put_byte(0x80);
-  while (M.off < nb * 64 - 8) M.put_byte(0);
-  M.put_word(0u);
-  M.put_word(len * 8u);
-  uint32_t st[8], w[16];
-  sha256_init(st);
-  for (uint32_t b = 0; b < nb; b++) {
-#pragma unroll
-    for (int k = 0; k < 16; k++) w[k] = M.word(16 * b + k);
-    sha256_compress(st, w);
-  }
-  const uint32_t* D = draws + (size_t)i * IDG_ND * 8;
-  uint32_t c1[8];
+  uint32_t c1[8], nonce[8];
   T c;
-  CV::digest_mod_r(st, c1);
-  // c = HashToZr(Zr.Bytes(c') || Zr.Bytes(nonce))
+  sink_digest<CV>(M, c1);
+  const uint32_t* D = draws + (size_t)i * IDG_ND * 8;
 #pragma unroll
-  for (int k = 0; k < 8; k++) w[k] = c1[7 - k];
-#pragma unroll
-  for (int k = 0; k < 8; k++) w[8 + k] = D[8 * GD_NONCE + 7 - k];
-  sha256_init(st);
-  sha256_compress(st, w);
-  w[0] = 0x80000000u;
-#pragma unroll
-  for (int k = 1; k < 15; k++) w[k] = 0u;
-  w[15] = 512u;
-  sha256_compress(st, w);
-  CV::digest_mod_r(st, c.v);
+  for (int k = 0; k < 8; k++) nonce[k] = D[8 * GD_NONCE + 7 - k];  // a draw: LE limbs
+  nonce_challenge<CV>(c1, nonce, c.v);
   const T cm = Z::to_mont(c);
   uint32_t* S = O + 16 * 6;
   auto put = [&](int slot, const T& v) {

@@ -22,23 +22,6 @@
 
 namespace idv {
 
-// SHA-256 blocks of a string of len bytes (no 32-bit overflow up to the API's 0xffffff00)
-FTS_DEV uint32_t audit_sha_blocks(uint32_t len) { return len / 64u + 1u + ((len % 64u) >= 56u ? 1u : 0u); }
-
-// big-endian word j of the padded stream of nb blocks over the string m (its bytes in
-// whole words, zero-filled, one spare word: host staging)
-FTS_DEV uint32_t audit_stream_word(const uint32_t* __restrict__ m, uint32_t len, uint32_t nb, uint32_t j) {
-  if (j == 16u * nb - 2u) return len >> 29;  // the bit length, 64 bits
-  if (j == 16u * nb - 1u) return len << 3;
-  const uint64_t b = 4ull * j;
-  if (b > len) return 0u;
-  if (b == len) return 0x80000000u;
-  const uint32_t raw = __builtin_bswap32(m[j]);
-  if (b + 4 <= len) return raw;
-  const uint32_t keep = len - (uint32_t)b;  // 1..3 bytes
-  return (raw & (0xffffffffu << (32 - 8 * keep))) | (0x80000000u >> (8 * keep));
-}
-
 // pts, rnd: [2][n] raw points (X || Y) and rands (32 B big-endian); attrw + aoff[g]:
 // lane g's string, alen[g] bytes; pre[n]: the host's verdicts that end a match;
 // rh_pre[n]: the RH half's verdict as far as the host knows it (no nym, a coordinate
@@ -74,12 +57,12 @@ __global__ void __launch_bounds__(64) k_idv_audit(int n, const uint8_t* __restri
   }
   // HashToZr(attribute)
   const uint32_t* m = attrw + aoff[g];
-  const uint32_t len = alen[g], nb = audit_sha_blocks(len);
+  const uint32_t len = alen[g], nb = padded_blocks(len);
   uint32_t st[8], w[16];
   sha256_init(st);
   for (uint32_t blk = 0; blk < nb; blk++) {
 #pragma unroll
-    for (int k = 0; k < 16; k++) w[k] = audit_stream_word(m, len, nb, 16u * blk + k);
+    for (int k = 0; k < 16; k++) w[k] = padded_word(m, 0u, len, nb, 16u * blk + k);
     sha256_compress(st, w);
   }
   uint32_t h[8], r[8];

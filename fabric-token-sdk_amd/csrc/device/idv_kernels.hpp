@@ -22,7 +22,7 @@
 //                  lines of W and g2, multi-Miller loop, final exponentiation)
 // Curves: BN254 (gnark; G1 64-byte raw encodings, 16-bit signed fixed-base
 // tables) and FP256BN (AMCL; 0x04 || X || Y, 16-bit unsigned tables), behind a
-// traits struct each.  Kernels, device tables and the launch_*<CV> templates only:
+// traits struct each (idemix_curves.hpp).  Kernels, device tables and the launch_*<CV> templates only:
 // idemix_identity_<cv>.hip, idemix_pairing_<cv>.hip and idemix_bp_<cv>.hip instantiate
 // one curve's launch sequences each (a curve's two pairing kernels are minutes of device
 // compilation each; the units build in parallel), and the host code (api_idemix.cpp)
@@ -35,12 +35,8 @@
 
 #include "../../../include/fts_gpu.h"
 #include "../common/chacha20.hpp"
-#include "../common/sha256.hpp"
-#include "fixed_base.hpp"
-#include "glv.hpp"
-#include "helpers.hpp"
-#include "transcript.hpp"
-#include "fp256bn.hpp"
+#include "idemix_curves.hpp"  // BnCurve, FbnCurve, Zr, LaneWords, ByteSink
+#include "idemix_hash.hpp"    // sink_digest, nonce_challenge, padded_word
 #include "pairing.hpp"
 #include "launch.hpp"
 #include "../host/idemix_parse.hpp"  // the record layout (NPT, P_*, R_*, F_*, ...)
@@ -65,152 +61,6 @@ __device__ constexpr int FIX_T2[NFIX] = {-1, -1, 2, -1, -1, 3, 4, -1, -1, -1, -1
 // transcript: label || t1 t2 t3 A' ABar B' Nym EidNym t4 RhNym t5 || ipk.Hash || Disclosure (4 zero bytes)
 constexpr char LABEL[] = "signWithEidNymRhNym";
 constexpr int LABEL_LEN = 19;
-
-// ----------------------------------------------------------- curve traits
-// BN254 (gnark-crypto through mathlib): G1.Bytes() = 64-byte raw X || Y, 64 zero
-// bytes = identity; fixed-base tables of fixed_base.hpp (signed 16-bit windows)
-struct BnCurve {
-  using B = pair::BnField;
-  using F = Fp;
-  using PJ = G1J;
-  static constexpr int G1_BYTES = 64;
-  static constexpr bool HOST_MONT = true;  // the host hands points over in Montgomery form (host/bn254_host.hpp)
-  static FTS_DEV PJ inf() { return g1j_identity(); }
-  static FTS_DEV bool is_inf(const PJ& p) { return f_is_zero(p.z); }
-  static FTS_DEV PJ dbl(const PJ& p) { return g1j_dbl(p); }
-  static FTS_DEV void add_to(PJ& acc, const PJ& q) { add_inl(acc, q); }
-  static FTS_DEV void madd_to(PJ& acc, const F& x, const F& y) {
-    G1A q;
-    q.x = x, q.y = y;
-    madd_inl(acc, q);
-  }
-  static FTS_DEV PJ from_affine(const F& x, const F& y) {
-    PJ r;
-    r.x = x, r.y = y, r.z = f_one<FpP>();
-    return r;
-  }
-  // raw BE X || Y -> affine Montgomery; NewG1FromBytes rules (canonical, on the curve; zeros = identity)
-  static FTS_DEV bool decode(const uint8_t* raw, F& x, F& y, bool& ident) {
-    G1A a;
-    const bool ok = decode_point(raw, a);
-    ident = ok && g1a_is_identity(a);
-    x = a.x, y = a.y;
-    return ok;
-  }
-  // affine Montgomery (identity: zeros) -> G1.Bytes()
-  template <class Sink>
-  static FTS_DEV void encode(Sink& s, const F& x, const F& y) {
-    uint32_t pw[16];
-    g1_mont_to_be_words(x, y, pw);
-    for (int k = 0; k < 16; k++) s.put_word(pw[k]);
-  }
-  static FTS_DEV void fixed_mul_acc(PJ& acc, const uint32_t* tables, int base, const uint32_t* k) {
-    Scalar s;
-#pragma unroll
-    for (int q = 0; q < 8; q++) s.v[q] = k[q];
-    fb_mul_acc_jac(acc, tables + (size_t)base * FB_WORDS_PER_BASE, s);  // Jacobian: k_idv_var's registers
-  }
-  static FTS_DEV void decompose(const uint32_t k[8], uint32_t k1[4], uint32_t& s1, uint32_t k2[4], uint32_t& s2) {
-    glv_decompose<Glv>(k, k1, s1, k2, s2);
-  }
-  static FTS_DEV F beta() { return glv_beta(); }
-  // HashToZr of a digest -> canonical LE limbs
-  static FTS_DEV void digest_mod_r(const uint32_t st[8], uint32_t out[8]) {
-    const Fr r = digest_to_fr(st);
-#pragma unroll
-    for (int q = 0; q < 8; q++) out[q] = r.v[q];
-  }
-};
-
-// FP256BN (AMCL through mathlib): G1.Bytes() = 0x04 || X || Y; decoded points
-// must be canonical and on the curve (no identity encoding); fixed-base tables
-// of idemix_kernels.hip (unsigned 16-bit windows, 2^16 entries)
-constexpr int FBN_NW = 16, FBN_ND = 1 << 16;
-struct FbnCurve {
-  using B = pair::FbnField;
-  using F = fbn::Fp;
-  using PJ = fbn::PJ;
-  static constexpr int G1_BYTES = 65;
-  static constexpr bool HOST_MONT = false;  // the host hands over plain LE limbs (no Montgomery code for this p there)
-  static FTS_DEV PJ inf() { return fbn::pj_inf(); }
-  static FTS_DEV bool is_inf(const PJ& p) { return fbn::is_zero(p.z); }
-  static FTS_DEV PJ dbl(const PJ& p) { return fbn::pj_dbl(p); }
-  static FTS_DEV void add_to(PJ& acc, const PJ& q) { acc = fbn::pj_add(acc, q); }
-  static FTS_DEV void madd_to(PJ& acc, const F& x, const F& y) { acc = fbn::pj_madd(acc, x, y); }
-  static FTS_DEV PJ from_affine(const F& x, const F& y) {
-    PJ r;
-    r.x = x, r.y = y, r.z = fbn::load<fbn::PM>(fbn::PM::ONE);
-    return r;
-  }
-  static FTS_DEV bool decode(const uint8_t* raw, F& x, F& y, bool& ident) {
-    uint32_t pw[16];
-    load_be_words(raw, pw);
-    uint32_t nx[8], ny[8];
-#pragma unroll
-    for (int k = 0; k < 8; k++) nx[k] = pw[7 - k], ny[k] = pw[15 - k];
-    ident = false;
-    if (!p256::lt256(nx, fbn::PM::M) || !p256::lt256(ny, fbn::PM::M)) return false;
-    x = p256::to_mont(fbn::load<fbn::PM>(nx));
-    y = p256::to_mont(fbn::load<fbn::PM>(ny));
-    return fbn::on_curve(x, y);
-  }
-  template <class Sink>
-  // AMCL ECP.ToBytes(b, false): the point at infinity (held here as (0, 0)) is
-  // AMCL's projective (0, 1, 0), which Affine() leaves as is -> 0x04 || 0 || 1
-  static FTS_DEV void encode(Sink& s, const F& x, const F& y) {
-    s.put_byte(0x04);
-    const F ax = p256::from_mont(x);
-    F ay = p256::from_mont(y);
-    if (fbn::is_zero(ax) && fbn::is_zero(ay)) ay.v[0] = 1u;
-    for (int k = 7; k >= 0; k--) s.put_word(ax.v[k]);
-    for (int k = 7; k >= 0; k--) s.put_word(ay.v[k]);
-  }
-  static FTS_DEV void fixed_mul_acc(PJ& acc, const uint32_t* tables, int base, const uint32_t* k) {
-    const uint32_t* tb = tables + (size_t)base * FBN_NW * FBN_ND * 16;
-    for (int w = 0; w < FBN_NW; w++) {
-      const uint32_t d = (k[w >> 1] >> (16 * (w & 1))) & 0xffffu;
-      if (d) {
-        const uint32_t* t = tb + ((size_t)w * FBN_ND + d) * 16;
-        acc = fbn::pj_madd(acc, fbn::load<fbn::PM>(t), fbn::load<fbn::PM>(t + 8));
-      }
-    }
-  }
-  static FTS_DEV void decompose(const uint32_t k[8], uint32_t k1[4], uint32_t& s1, uint32_t k2[4], uint32_t& s2) {
-    glv_decompose<fbn::GlvK>(k, k1, s1, k2, s2);
-  }
-  static FTS_DEV F beta() { return fbn::load<fbn::PM>(fbn::GlvK::BETA); }
-  static FTS_DEV void digest_mod_r(const uint32_t st[8], uint32_t out[8]) {
-    uint32_t t[8], bw = 0;
-#pragma unroll
-    for (int i = 0; i < 8; i++) out[i] = st[7 - i];
-#pragma unroll
-    for (int i = 0; i < 8; i++) t[i] = subb(out[i], fbn::RM::M[i], bw, bw);
-#pragma unroll
-    for (int i = 0; i < 8; i++) out[i] = bw ? out[i] : t[i];
-  }
-};
-
-// ------------------------------------------------------------ lane scratch
-// [unit][lane] layouts: neighbouring lanes touch neighbouring addresses
-struct LaneWords {
-  uint32_t* base;
-  size_t L, lane;
-  FTS_DEV uint32_t& at(size_t w) const { return base[w * L + lane]; }
-};
-// transcript bytes, [byte][lane]
-struct ByteSink {
-  uint8_t* base;
-  size_t L, lane;
-  uint32_t off = 0;
-  FTS_DEV void put_byte(uint32_t b) { base[(size_t)(off++) * L + lane] = (uint8_t)b; }
-  FTS_DEV void put_word(uint32_t w) {  // big-endian
-    put_byte(w >> 24), put_byte(w >> 16), put_byte(w >> 8), put_byte(w);
-  }
-  FTS_DEV uint32_t word(uint32_t j) const {
-    const uint8_t* p = base + (size_t)(4 * j) * L + lane;
-    return ((uint32_t)p[0] << 24) | ((uint32_t)p[L] << 16) | ((uint32_t)p[2 * L] << 8) | p[3 * L];
-  }
-};
 
 // affine lane table of 1..8 * P: XY rows [8][L][16] | Z, PRE [16][8][L] words (GTab)
 constexpr int AT_WORDS = 8 * 16 + 8 * 8 + 8 * 8;
@@ -675,35 +525,9 @@ __global__ void __launch_bounds__(256) k_idv_tvals(int n, const uint32_t* __rest
   }
   for (int k = 0; k < 8; k++) M.put_word(ipk_hash[k]);
   M.put_word(0u);  // Disclosure: four hidden attributes
-  const uint32_t len = M.off;
-  // SHA-256 padding
-  const uint32_t nb = sha_blocks(len);
-  M.put_byte(0x80);
-  while (M.off < nb * 64 - 8) M.put_byte(0);
-  M.put_word(0u);
-  M.put_word(len * 8u);
-  uint32_t st[8], w[16];
-  sha256_init(st);
-  for (uint32_t b = 0; b < nb; b++) {
-#pragma unroll
-    for (int k = 0; k < 16; k++) w[k] = M.word(16 * b + k);
-    sha256_compress(st, w);
-  }
   uint32_t c1[8], c2[8];
-  CV::digest_mod_r(st, c1);
-  // c'' = HashToZr(Zr.Bytes(c') || Zr.Bytes(Nonce))
-#pragma unroll
-  for (int k = 0; k < 8; k++) w[k] = c1[7 - k];
-#pragma unroll
-  for (int k = 0; k < 8; k++) w[8 + k] = R[R_NONCE + k];
-  sha256_init(st);
-  sha256_compress(st, w);
-  w[0] = 0x80000000u;
-#pragma unroll
-  for (int k = 1; k < 15; k++) w[k] = 0u;
-  w[15] = 512u;
-  sha256_compress(st, w);
-  CV::digest_mod_r(st, c2);
+  sink_digest<CV>(M, c1);
+  nonce_challenge<CV>(c1, R + R_NONCE, c2);
   uint32_t diff = (flags & F_C_BIG) ? 1u : 0u;
 #pragma unroll
   for (int k = 0; k < 8; k++) diff |= c2[k] ^ R[R_C + k];

@@ -119,11 +119,11 @@ void launch_token_commit(int n, int per_lane, const uint32_t* sc, const uint32_t
 // ---- idemix_kernels.hip (nym signatures; the FP256BN fixed-base tables also serve the identity proofs)
 void fbn_build_tables(const uint32_t* plain, int nb, uint32_t* mont, int32_t* ok, uint32_t* tables, hipStream_t s);
 size_t fbn_words_per_base();
-// one tile of k_nym_verify (bn; msgw = the messages) or k_nym_verify_fbn (msgw = the hashed streams, ipk_hash unused)
+// one tile of k_nym_verify (bn; msgw = the messages) or k_nym_verify<FbnCurve> (msgw = the hashed streams, ipk_hash unused)
 void launch_nym_verify(bool bn, int n, const uint32_t* rec, const uint8_t* nym, const uint32_t* msgw,
                        const uint64_t* moff, const uint32_t* mlen, const uint32_t* tables, const uint32_t* ipk_hash,
                        uint32_t* vtab, int32_t* status, int base, int tile, hipStream_t s);
-// k_nym_sign (bn) or k_nym_sign_fbn over all n items: srec idv::NSREC words per item, out idv::NSOUT
+// k_nym_sign<BnCurve> (bn) or k_nym_sign<FbnCurve> over all n items: srec idv::NSREC words per item, out idv::NSOUT
 void launch_nym_sign(bool bn, int n, const uint32_t* srec, const uint8_t* nym, const uint32_t* msgw,
                      const uint64_t* moff, const uint32_t* mlen, const uint32_t* tables, const uint32_t* ipk_hash,
                      int32_t* status, uint32_t* out, hipStream_t s);

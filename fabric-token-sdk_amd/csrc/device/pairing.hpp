@@ -18,57 +18,15 @@
 // oracle/pairing_tower.py, whose result equals the direct E(Fp12) pairing of
 // oracle/pairing.py (pinned by the reference's credential fixtures).
 //
-// The field is abstracted by an adapter (BnField: fts::Fp with the grouped-MAC
-// product; FbnField: the full-width Montgomery code of p256.hpp on FP256BN's p).
+// The field is abstracted by an adapter (pair::BnField, pair::FbnField), defined
+// with the curve traits in idemix_curves.hpp.
 #pragma once
 #include "g1.hpp"
 #include "fp256bn.hpp"
 #include "pairing_consts.hpp"
+#include "idemix_curves.hpp"
 
 namespace pair {
-
-struct BnField {
-  using F = fts::Fp;
-  using K = pairc::Bn254;
-  static FTS_DEV F add(const F& a, const F& b) { return fts::f_add(a, b); }
-  static FTS_DEV F sub(const F& a, const F& b) { return fts::f_sub(a, b); }
-  static FTS_DEV F neg(const F& a) { return fts::f_neg(a); }
-  // (the two-accumulator product f_mul_fips2 made k_idv_pairing slower, 21.9 ->
-  // 26.7 ms per 65,536 identities: its extra column adds cost more than the
-  // shorter MAD chain saves, even at one wave per SIMD)
-  static FTS_DEV F mul(const F& a, const F& b) { return fts::fp_mul(a, b); }
-  static FTS_DEV F zero() { return fts::f_zero<fts::FpP>(); }
-  static FTS_DEV F one() { return fts::f_one<fts::FpP>(); }
-  static FTS_DEV bool is_zero(const F& a) { return fts::f_is_zero(a); }
-  static FTS_DEV bool eq(const F& a, const F& b) { return fts::f_eq(a, b); }
-  static FTS_DEV F inv(const F& a) { return fts::nl_fp_inv(a); }
-  static FTS_DEV F ld(const uint32_t* w) {
-    F r;
-#pragma unroll
-    for (int i = 0; i < 8; i++) r.v[i] = w[i];
-    return r;
-  }
-};
-
-struct FbnField {
-  using F = fbn::Fp;
-  using K = pairc::Fp256bn;
-  static FTS_DEV F add(const F& a, const F& b) { return p256::add(a, b); }
-  static FTS_DEV F sub(const F& a, const F& b) { return p256::sub(a, b); }
-  static FTS_DEV F zero() {
-    F r;
-#pragma unroll
-    for (int i = 0; i < 8; i++) r.v[i] = 0;
-    return r;
-  }
-  static FTS_DEV F neg(const F& a) { return p256::sub(zero(), a); }
-  static FTS_DEV F mul(const F& a, const F& b) { return p256::mul(a, b); }
-  static FTS_DEV F one() { return p256::load<fbn::PM>(fbn::PM::ONE); }
-  static FTS_DEV bool is_zero(const F& a) { return p256::is_zero(a); }
-  static FTS_DEV bool eq(const F& a, const F& b) { return p256::eq(a, b); }
-  static FTS_DEV F inv(const F& a) { return p256::inv(a); }
-  static FTS_DEV F ld(const uint32_t* w) { return p256::load<fbn::PM>(w); }
-};
 
 // ------------------------------------------------------------------- Fp2
 template <class B>

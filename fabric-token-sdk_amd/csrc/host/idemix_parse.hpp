@@ -87,6 +87,37 @@ inline int32_t parse_nym_sig(const uint8_t* sig, size_t len, bool bn, uint32_t* 
   return FTS_OK;
 }
 
+// Staging of one nym item for k_nym_verify / k_nym_sign.  The kernels read the hashed
+// stream's tail from HBM as aligned words: BN254 the message alone (the 164-byte prefix
+// is whole words, from registers), FP256BN the whole stream
+// "sign" || 0x04 || t (64 zero bytes: the device's) || Nym (65) || ipk.Hash || msg.
+constexpr size_t NYM_PRE_FBN = 166;
+// words of an item's region: its bytes in whole words, zero-filled, and one spare word
+inline size_t nym_stream_words(bool bn, size_t msg_len) { return ((bn ? 0 : NYM_PRE_FBN) + msg_len + 3) / 4 + 1; }
+// nym_slot (64 bytes) <- X || Y, mw (nym_stream_words words) <- the region, *len <- its
+// bytes; false (slot and Nym zeroed): a key of the wrong length or form.  NymPublicKey
+// import (crypto/deserializer.go:49-56): BN254 G1.Bytes() raw X || Y (64 B), FP256BN
+// ECP.ToBytes 0x04 || X || Y (65 B); the point checks run on the device.
+inline bool pack_nym_item(bool bn, const uint8_t* nym, size_t nym_len, const uint8_t ipk_hash[32], const uint8_t* msg,
+                          size_t msg_len, uint8_t* nym_slot, uint8_t* mw, uint32_t* len) {
+  const size_t pre = bn ? 0 : NYM_PRE_FBN;
+  const bool key_ok = nym && (bn ? nym_len == 64 : nym_len == 65 && nym[0] == 0x04);
+  if (key_ok) memcpy(nym_slot, nym + (bn ? 0 : 1), 64);
+  else memset(nym_slot, 0, 64);
+  *len = (uint32_t)(pre + msg_len);
+  if (!bn) {
+    memcpy(mw, "sign", 4);
+    mw[4] = 0x04;
+    memset(mw + 5, 0, 64);
+    if (key_ok) memcpy(mw + 69, nym, 65);
+    else memset(mw + 69, 0, 65);
+    memcpy(mw + 134, ipk_hash, 32);
+  }
+  if (msg_len) memcpy(mw + pre, msg, msg_len);
+  memset(mw + pre + msg_len, 0, nym_stream_words(bn, msg_len) * 4 - pre - msg_len);
+  return key_ok;
+}
+
 // SerializedIdemixIdentity + its Signature proto -> record, raw points, epoch key;
 // returns the identity-level status (FTS_OK: to the device)
 inline int32_t parse_identity(const uint8_t* id, size_t len, bool bn, uint32_t* rec, uint8_t* pts, uint8_t* epk) {

@@ -7,6 +7,8 @@
 //   arith_check --list   the op catalogue ("name operands results"), no device
 //   arith_check --list-chain   the same for the com chain's op (straus4_ctab:
 //                        tests/com_chain_vectors.py), kept apart from the primitives' list
+//   arith_check --list-glv     the same for the FP256BN GLV chain's op (fbn_glv_mul: tests/arith_vectors.py
+//                        FBN_GLV_KS)
 //   arith_check --list-fb      the same for the fixed-base ops (tests/fixed_base_vectors.py):
 //                        the signed-digit recoding and the table products of fixed_base.hpp
 //
@@ -42,6 +44,7 @@
 #include <string>
 #include <vector>
 #include "../device/glv.hpp"
+#include "../device/fbn_glv.hpp"
 #include "../device/pairing.hpp"
 #include "../host/bn254_host.hpp"
 
@@ -211,6 +214,9 @@ OP(FbMulAccJac, 4, 3, fts::G1J p = ldj(a, 0); fts::fb_mul_acc_jac(p, x.tab, ld<f
 // GLV decomposition (glv.hpp): k -> |k1|, s1, |k2|, s2
 TOP(K, GlvDec, 1, 4, uint32_t k1[4]; uint32_t k2[4]; uint32_t s1; uint32_t s2; fts::glv_decompose<K>(a, k1, s1, k2, s2);
     st4(r, 0, k1); stw(r, 1, s1); st4(r, 2, k2); stw(r, 3, s2););
+
+// the FP256BN nym kernels' variable-base product (fbn_glv.hpp) over the lane tables of glv_mul
+OP(FbnGlvMul, 3, 3, stpj(r, fbn::glv_mul_tab(ld<fbn::Fp>(a, 0), ld<fbn::Fp>(a, 1), a + 16, x.tab, x.n, i)););
 
 // P-256 and FP256BN points (p256.hpp, fp256bn.hpp)
 OP(P256Dbl, 3, 3, stpj(r, p256::pj_dbl(ldpj<p256::PJ>(a, 0))););
@@ -446,6 +452,14 @@ static std::vector<Entry> chain_ops() {
   return c;
 }
 
+// the FP256BN chain's op, listed by --list-glv, apart for the reason chain_ops gives.  Q on
+// the curve is the test's business (there is no host code for this p)
+static std::vector<Entry> glv_ops() {
+  std::vector<Entry> c;
+  c.push_back(E<FbnGlvMul>("fbn_glv_mul", "445", nullptr, true));
+  return c;
+}
+
 // the fixed-base ops: listed by --list-fb (tests/fixed_base_vectors.py), apart from the
 // primitives' catalogue for the reason chain_ops gives.  fb_mul2_same and fb_mul2_neg are
 // fb_mul2 under names of their own, so that each has tables of its own (the second a
@@ -529,7 +543,7 @@ struct Batch {
 
 int main(int argc, char** argv) {
   std::vector<Entry> cat = catalogue();
-  const std::vector<Entry> chain = chain_ops(), fb = fb_ops();
+  const std::vector<Entry> chain = chain_ops(), fb = fb_ops(), glv = glv_ops();
   if (argc == 2 && !strcmp(argv[1], "--list")) {
     for (const Entry& e : cat) printf("%s %d %d\n", e.name, e.ni, e.no);
     return 0;
@@ -542,10 +556,15 @@ int main(int argc, char** argv) {
     for (const Entry& e : fb) printf("%s %d %d\n", e.name, e.nwords(), e.no);
     return 0;
   }
+  if (argc == 2 && !strcmp(argv[1], "--list-glv")) {
+    for (const Entry& e : glv) printf("%s %d %d\n", e.name, e.ni, e.no);
+    return 0;
+  }
   cat.insert(cat.end(), chain.begin(), chain.end());
+  cat.insert(cat.end(), glv.begin(), glv.end());
   cat.insert(cat.end(), fb.begin(), fb.end());
   if (argc != 3) {
-    fprintf(stderr, "usage: %s IN OUT | --list | --list-chain | --list-fb\n", argv[0]);
+    fprintf(stderr, "usage: %s IN OUT | --list | --list-chain | --list-fb | --list-glv\n", argv[0]);
     return 2;
   }
   FILE* fi = fopen(argv[1], "r");

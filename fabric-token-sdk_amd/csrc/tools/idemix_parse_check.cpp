@@ -9,6 +9,7 @@
 //   idemix_parse_check <file of lines: kind curve hex [honest|tile]>
 //     kind: id | nym | ipk | audit; curve: bn254 | fp256bn; honest, tile: an honest golden case
 //     (audit: an identity read by parse_audit_identity, the audit-info matcher's parser)
+//   first checks the nym items' staging (check_pack) and prints "pack <cases> cases";
 //   prints "audit <input index> <pre> <rh_pre>" for every audit input as given, then a
 //   SHA-256 over every output of the run; exit status 0 iff every check holds
 #include <atomic>
@@ -196,6 +197,57 @@ static Result run_input(const Input& in) {
   return r;
 }
 
+// ---- the nym items' staging (pack_nym_item, nym_stream_words) into exactly-sized blocks,
+// against the layout written out here: both curves, message lengths 0..5 (every fill to
+// the word boundary), a null message of length 0, a nym of the wrong length and an
+// FP256BN nym without its 0x04.  Returns the number of cases.
+static int check_pack() {
+  int cases = 0;
+  uint8_t hash[32], key[65], text[5];
+  for (int k = 0; k < 32; k++) hash[k] = (uint8_t)(0xa0 + k);
+  for (int k = 0; k < 65; k++) key[k] = (uint8_t)(k + 1);
+  for (int k = 0; k < 5; k++) text[k] = (uint8_t)(0xf1 + k);
+  for (bool bn : {true, false}) {
+    const size_t klen = bn ? 64 : 65;
+    key[0] = bn ? 0x01 : 0x04;
+    for (int form = 0; form < 4; form++) {  // 0 good, 1 short, 2 null, 3 FP256BN without the 0x04
+      if (form == 3 && bn) continue;
+      for (size_t ml = 0; ml <= 5; ml++)
+        for (bool null_msg : {false, true}) {
+          if (null_msg && ml) continue;
+          const bool good = form == 0;
+          const auto nym = exact(key, form == 1 ? klen - 1 : klen);
+          if (form == 3) nym[0] = 0x02;
+          const auto msg = exact(text, ml);
+          const size_t pre = bn ? 0 : 166, words = (pre + ml + 3) / 4 + 1;
+          CHECK(nym_stream_words(bn, ml) == words);
+          std::unique_ptr<uint8_t[]> slot(new uint8_t[64]), mw(new uint8_t[words * 4]);
+          memset(slot.get(), 0xee, 64);
+          memset(mw.get(), 0xee, words * 4);
+          uint32_t len = 0;
+          const bool ok = pack_nym_item(bn, form == 2 ? nullptr : nym.get(), form == 1 ? klen - 1 : klen, hash,
+                                        null_msg ? nullptr : msg.get(), ml, slot.get(), mw.get(), &len);
+          std::vector<uint8_t> want_slot(64, 0), want;
+          if (good) want_slot.assign(key + (bn ? 0 : 1), key + klen);
+          if (!bn) {
+            want = {'s', 'i', 'g', 'n', 0x04};
+            want.resize(69, 0);
+            if (good) want.insert(want.end(), key, key + 65);
+            want.resize(134, 0);
+            want.insert(want.end(), hash, hash + 32);
+          }
+          want.insert(want.end(), text, text + ml);
+          want.resize(words * 4, 0);
+          CHECK(ok == good && len == pre + ml);
+          CHECK(memcmp(slot.get(), want_slot.data(), 64) == 0);
+          CHECK(memcmp(mw.get(), want.data(), words * 4) == 0);
+          cases++;
+        }
+    }
+  }
+  return cases;
+}
+
 // the inputs' digests in input order -> the run's digest
 static std::string run_all(const std::vector<Input>& in, size_t threads, size_t& calls, std::vector<Result>& res) {
   res.assign(in.size(), Result());
@@ -243,6 +295,7 @@ int main(int argc, char** argv) {
     in.push_back(x);
   }
   CHECK(!in.empty());
+  printf("idemix_parse_check: pack %d cases\n", check_pack());
   size_t calls = 0, calls4 = 0;
   std::vector<Result> res, res4;
   const std::string serial = run_all(in, 1, calls, res), threaded = run_all(in, 4, calls4, res4);

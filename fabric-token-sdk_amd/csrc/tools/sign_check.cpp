@@ -8,6 +8,10 @@
 //   km  <x> <message hex|->   the nonce for SHA-256(message)
 //   der <r> <s>               the DER signature
 //   nym <c> <s_sk> <s_r> <nonce>   the NymSignature proto
+//   pad <prefix hex|-> <tail hex|->   SHA-256 of prefix || tail with the padded stream assembled
+//                             by padded_word / padded_blocks (common/sha_padding.hpp, the nym and
+//                             audit kernels' code); exit status 2 if the streaming hash differs
+//   blocks <len, 4 B>         padded_blocks(len), 4 B
 // Every output buffer is a heap block of exactly its size.  Exit status 0 iff every
 // line was understood.
 #include <cstdio>
@@ -18,6 +22,7 @@
 #include <vector>
 
 #include "../common/hmac_drbg.hpp"
+#include "../common/sha_padding.hpp"
 #include "../host/sign_encode.hpp"
 
 using namespace fts;
@@ -104,6 +109,41 @@ int main() {
       host::nym_sig_proto(a[0].data(), a[1].data(), a[2].data(), a[3].data(), out.get());
       put_hex(out.get(), host::NYM_SIG_LEN);
       printf("\n");
+    } else if (ok && cmd == "pad" && a.size() == 2 && a[0].size() % 4 == 0) {
+      // the stream as the kernels assemble it: the prefix's words from the caller, the
+      // rest through padded_word over a block of exactly the staged size
+      const uint32_t pre = (uint32_t)a[0].size(), len = (uint32_t)a[1].size(), nb = padded_blocks(pre + len);
+      const size_t mw = (len + 3) / 4 + 1;
+      std::unique_ptr<uint32_t[]> m(new uint32_t[mw]);
+      memset(m.get(), 0, mw * 4);
+      if (len) memcpy(m.get(), a[1].data(), len);
+      uint32_t st[8], w[16];
+      sha256_init(st);
+      for (uint32_t blk = 0; blk < nb; blk++) {
+        for (uint32_t k = 0; k < 16; k++) {
+          const uint32_t g = 16 * blk + k;
+          if (g < pre / 4) {
+            const uint8_t* p = a[0].data() + 4 * g;
+            w[k] = ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | p[3];
+          } else {
+            w[k] = padded_word(m.get(), pre, len, nb, g);
+          }
+        }
+        sha256_compress(st, w);
+      }
+      // against the byte-streaming hash of the same bytes
+      std::vector<uint8_t> all(a[0]);
+      all.insert(all.end(), a[1].begin(), a[1].end());
+      uint8_t dg[32];
+      uint32_t want[8];
+      sha256(all.data(), all.size(), dg);
+      words(dg, want);
+      if (memcmp(st, want, 32) != 0) return 2;
+      put_words(st);
+      printf("\n");
+    } else if (ok && cmd == "blocks" && a.size() == 1 && a[0].size() == 4) {
+      const uint32_t len = ((uint32_t)a[0][0] << 24) | ((uint32_t)a[0][1] << 16) | ((uint32_t)a[0][2] << 8) | a[0][3];
+      printf("%08x\n", padded_blocks(len));
     } else {
       bad++;
     }

@@ -11,7 +11,7 @@ Mirrors services/identity/idemix/crypto/id.go:145-161:
 
 Signing: ``IssuerKey.sign_batch(sks, rnyms, nyms, msgs)`` and
 ``NymSigner(issuer_key, sk, rnym, nym).Sign(message)`` produce the NymSignature
-protos that the verifiers above accept (k_nym_sign / k_nym_sign_fbn).
+protos that the verifiers above accept (k_nym_sign<BnCurve> / k_nym_sign<FbnCurve>).
 
 Identities: ``IdentityVerifier`` checks owner identities and matches audit info against
 them; ``Credential(verifier, cred, sk).generate(n)`` produces them on the device
@@ -22,7 +22,7 @@ credentials as NewKeyManager does, pairing equation included (km.go:117-133).
 The issuer key is the idemix IssuerPublicKey proto a zkatdlog PublicParams
 carries, on BN254 (the tokengen key of zkatdlog_pp.json) or FP256BN_AMCL (the
 validator's test keys).  There is no CPU fallback: every verdict comes from
-the HIP kernel k_nym_verify.
+the HIP kernels k_nym_verify (BN254, idemix_kernels.hip) and k_nym_verify<FbnCurve> (device/nym_kernels.hpp).
 """
 import ctypes as C
 

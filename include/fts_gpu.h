@@ -672,7 +672,7 @@ int fts_nym_verify_batch(fts_idemix_ipk* ipk, size_t n, const fts_nym_item* item
 /* Host-only: SerializedIdemixIdentity.nym_public_key (idemix/crypto/protos/idemix_config.proto,
  * crypto/deserializer.go:41-56); *nym points into `id`. FTS_API_EINVAL if absent or malformed. */
 int fts_idemix_identity_nym(const uint8_t* id, size_t len, const uint8_t** nym, size_t* nym_len);
-/* HIP-event duration (ms) of k_nym_verify in the last finished fts_nym_verify_batch on `ipk`. */
+/* HIP-event duration (ms) of k_nym_verify (BN254) / k_nym_verify<FbnCurve> in the last finished fts_nym_verify_batch on `ipk`. */
 int fts_nym_last_timings(fts_idemix_ipk* ipk, float* ms);
 
 /* ---- idemix pseudonym signing ----
@@ -699,7 +699,7 @@ typedef struct {
  * FTS_API_EINVAL for a NULL handle or argument, n > 2^24 or a NULL msg with a length. */
 int fts_nym_sign_batch(fts_idemix_ipk* ipk, size_t n, const fts_nym_sign_item* items, uint64_t seed, uint8_t* sig,
                        int32_t* status);
-/* HIP-event duration (ms) of k_nym_sign / k_nym_sign_fbn in the last finished fts_nym_sign_batch. */
+/* HIP-event duration (ms) of k_nym_sign<BnCurve> / k_nym_sign<FbnCurve> in the last finished fts_nym_sign_batch. */
 int fts_nym_sign_last_timings(fts_idemix_ipk* ipk, float* ms);
 
 /* ---- idemix identity validity (idemix half) ----

@@ -58,7 +58,10 @@ def _catalogue():
 
 
 CATALOGUE = _catalogue()
-ARITY = {n: (ni, no) for n, ni, no in CATALOGUE}
+# the FP256BN chain's op, listed by `arith_check --list-glv`: apart from the primitives' catalogue, which
+# stays as it is (as the com chain's and the fixed-base ops are)
+GLV_CATALOGUE = [("fbn_glv_mul", 3, 3)]
+ARITY = {n: (ni, no) for n, ni, no in CATALOGUE + GLV_CATALOGUE}
 
 
 # ------------------------------------------------------------ Montgomery helpers
@@ -200,7 +203,7 @@ def header_consts(header, struct):
 
 GLV_SETS = {"bn": ("glv.hpp", "Glv", bn.R, bn.P), "fbn": ("fp256bn.hpp", "GlvK", OI.FP256BNC.r, OI.FP256BNC.p)}
 # what the consuming chain can recode: 32 signed 4-bit windows with no carry out of the
-# top one (vb128j, straus2_128) / k_nym_verify_fbn's 33 windows, the 33rd taking the carry
+# top one (vb128j, straus2_128) / fbn::glv_mul_tab's 33 windows, the 33rd taking the carry
 GLV_BOUND = {"bn": 1 << 127, "fbn": 1 << 128}
 
 
@@ -494,6 +497,71 @@ def scalar_records():
             recs.append(("straus2_128", jac_words(C, A, zs[0]) + [a] + jac_words(C, Q, z) + [b], "jac:bn", want))
         want = bn.g1_mul(B, b) if b else None
         recs.append(("straus2_128", jac_words(C, None, 0) + [a] + jac_words(C, B, zs[2]) + [b], "jac:bn", want))
+    return recs
+
+
+# fbn::glv_mul_tab (fbn_glv.hpp, the FP256BN nym kernels' variable-base product): the
+# scalars by the property each has under glv_decompose.  The chain recodes |k1| and |k2|
+# into 33 signed 4-bit windows, the 33rd taking a carry out of nibble 31.  No k < r sends
+# one there: |k1| <= (A1 + A2) / 2 and |k2| <= (NB1 + A1) / 2, both 0x7fffffffffff3c33...
+# < 2^127, so nibble 31 is at most 7 and 7 + carry = 8 is kept as the digit +8.  A
+# magnitude whose nibbles are all 0xf does not exist (fbn_glv_search(0): no k among 10^6
+# seeded draws has 0xf in nibble 31 either), so in its place stand the two closest:
+# nibble 31 = 7 over the longest run of 0xf below it, which carries all the way up to
+# that digit +8.
+FBN_GLV_KS = [
+    (0, "zero: the identity"),
+    (1, "k1 = 1, k2 = 0"),
+    (2, "k1 = 2, k2 = 0"),
+    ("r-1", "k1 = -1, k2 = 0"),
+    ("lam", "k1 = 0, k2 = 1: phi(Q) alone"),
+    ("lam-1", "k1 = -1, k2 = 1"),
+    (0xaae8812bd2a9068a982e5c91f91ecb2b62bcfc1ea1b66a0cc3a24c99162c17a8,
+     "|k1| = 0x7ffff1...: the longest run of 0xf below nibble 31 = 7 in random.Random(128)'s first 10^6 "
+     "draws below r (fbn_glv_search(1)); k1 < 0 < k2"),
+    (0x7fffffffffff00000000000000000000,
+     "k1 = k, k2 = 0, eleven 0xf below nibble 31 = 7: the longest such run with k2 = 0 (constructed, no draw)"),
+    (5 << 100, "k2 = 0 with k1 of 103 bits: windows 26..32 of k1 and all of k2 are zero"),
+]
+
+
+def fbn_glv_search(below):
+    """the seeded search behind FBN_GLV_KS (seconds; not run by any test): the draw with the
+    longest run of 0xf nibbles of |k1| from nibble 31 - below downwards, nibble 31 largest first"""
+    hdr, st, r, _ = GLV_SETS["fbn"]
+    c = header_consts(hdr, st)
+    rng = random.Random(128)
+    best = (-1, -1, None)
+    for _ in range(10 ** 6):
+        k = rng.randrange(r)
+        key = _f_run(abs(glv_decompose(k, c)[0]), below)
+        if key > best[:2]:
+            best = key + (k,)
+    return best
+
+
+def _f_run(mag, below):
+    n, i = 0, 31 - below
+    while i >= 0 and (mag >> (4 * i)) & 15 == 15:
+        n, i = n + 1, i - 1
+    return (mag >> 124 if below else 0, n)
+
+
+def fbn_glv_scalars():
+    r, lam = OI.FP256BNC.r, glv_lambda("fbn")
+    named = {"r-1": r - 1, "lam": lam, "lam-1": lam - 1}
+    rng = random.Random(33)
+    return [named.get(k, k) for k, _ in FBN_GLV_KS] + [rng.randrange(r) for _ in range(8)]
+
+
+@functools.lru_cache(maxsize=None)
+def fbn_glv_records():
+    """operands Qx Qy (affine Montgomery, on the curve) and k < r; want: the oracle's k * Q"""
+    F, C = OI.FP256BNC, CURVES["fbn"]
+    recs = []
+    for P in (C.gen, F.mul((1, 2), 0x1f2e3d4c5b6a79880123456789abcdef)):
+        for k in fbn_glv_scalars():
+            recs.append(("fbn_glv_mul", aff_words(C, P) + [k], "jac:fbn", F.mul(P, k) if k else None))
     return recs
 
 

@@ -164,6 +164,34 @@ def test_glv_vectors():
     assert [(op, sum(1 for r_ in got if r_[0] == op)) for op, _ in want] == want
 
 
+def test_list_glv_names_the_op():
+    out = subprocess.run([EXE, "--list-glv"], capture_output=True, text=True, timeout=60)
+    assert out.returncode == 0, out.stderr
+    assert [(n, int(a), int(b)) for n, a, b in (l.split() for l in out.stdout.splitlines())] == AV.GLV_CATALOGUE
+
+
+def test_fbn_glv_mul_scalars_have_the_properties_noted():
+    """FBN_GLV_KS: each scalar decomposes as its note says, on-curve operands, and no k can
+    carry into window 32 (the lattice bound keeps nibble 31 of both halves at 7 or less)"""
+    hdr, st, r, p = AV.GLV_SETS["fbn"]
+    c = AV.header_consts(hdr, st)
+    assert (c["A1"] + c["A2"]) // 2 + 2 < 1 << 127 and (c["NB1"] + c["A1"]) // 2 + 2 < 1 << 127
+    ks = AV.fbn_glv_scalars()
+    dec = [AV.glv_decompose(k, c) for k in ks]
+    assert dec[:6] == [(0, 0), (1, 0), (2, 0), (-1, 0), (0, 1), (-1, 1)]
+    k1, k2 = dec[6]
+    assert abs(k1) >> 108 == 0x7ffff and k1 < 0 < k2
+    assert dec[7] == (0x7fffffffffff00000000000000000000, 0) and dec[8] == (5 << 100, 0)
+    assert all(abs(a) < 1 << 127 and abs(b) < 1 << 127 for a, b in dec)
+    recs = AV.fbn_glv_records()
+    assert len(recs) == 2 * len(ks) and len(ks) == len(AV.FBN_GLV_KS) + 8
+    C = AV.CURVES["fbn"]
+    for op, ins, kind, want in recs:
+        assert op == "fbn_glv_mul" and kind == "jac:fbn" and ins[2] < r
+        P = (AV.from_mont(ins[0], p), AV.from_mont(ins[1], p))
+        assert C.on(P) and want == (C.mul(ins[2], P) if ins[2] else None)
+
+
 def test_curve_arithmetic_agrees_with_the_oracle():
     from oracle import bn254 as bn, ecdsa_p256 as P2, idemix as OI
     rng = random.Random(2)

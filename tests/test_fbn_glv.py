@@ -1,5 +1,5 @@
 """FP256BN GLV constants of csrc/device/fp256bn.hpp (fbn::GlvK), used by
-k_nym_verify_fbn's (r - c)*Nym chain: read from the header and checked on the
+k_nym_verify<FbnCurve>'s (r - c)*Nym chain: read from the header and checked on the
 CPU against the oracle's curve (oracle/idemix.py FP256BNC): phi(x, y) =
 (beta x, y) equals lambda * P, and glv_decompose's Babai rounding (restated
 below limb for limb in integers) gives k = k1 + k2 lambda (mod r) with

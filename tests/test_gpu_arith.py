@@ -104,6 +104,20 @@ def test_scalar_products(run, op):
     _check(run, [op])
 
 
+def test_fbn_glv_mul(tmp_path):
+    """fbn::glv_mul_tab (device/fbn_glv.hpp), the FP256BN nym kernels' variable-base product,
+    against the oracle's k * Q: the scalars of AV.FBN_GLV_KS and eight random ones on two
+    points.  Its op is listed apart from the catalogue (--list-glv), so it has a run of its own"""
+    recs = AV.fbn_glv_records()
+    inp, outp = tmp_path / "in.txt", tmp_path / "out.txt"
+    inp.write_text(AV.format_records(recs))
+    out = subprocess.run([EXE, str(inp), str(outp)], capture_output=True, text=True, timeout=TIMEOUT_S)
+    assert out.returncode == 0, out.stdout + out.stderr
+    res = AV.parse_results(outp.read_text())
+    assert len(res) == len(recs) and all(len(w) == 3 for w in res)
+    _check({"fbn_glv_mul": list(zip(recs, res))}, ["fbn_glv_mul"])
+
+
 @pytest.mark.parametrize("tag", ["bn", "fbn"])
 def test_glv_decompose(run, tag):
     """the device Babai step equals the integer one limb for limb; with the returned

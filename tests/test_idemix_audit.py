@@ -98,6 +98,57 @@ def test_agrees_with_identity_verifier_on_one_handle(verifiers, doc, tag):
     assert e.value.status == I.FTS_E_AUDIT_EID_MISMATCH
 
 
+ATTR_LENS = [0, 1, 3, 4, 55, 56, 63, 64, 65, 119, 120, 127, 128]
+
+
+@pytest.mark.parametrize("tag", TAGS)
+def test_attribute_lengths_around_the_block_edges(verifiers, doc, tag):
+    """one batch whose eid / rh strings have the lengths where the padded stream's words
+    change shape (a partial last word, the terminator in a word of its own, the bit
+    length in a further block; the golden cases lack 3, 4, 127 and 128): honest_0 with
+    both nyms committing to synthetic strings, the eid's length ascending and the rh's
+    descending, then the same with the last byte of the longer string flipped; every
+    verdict is AuditInfo.Match's (tests/idemix_audit_ref.py)"""
+    import idemix_audit_ref as REF
+    from oracle import idemix as OI
+    C = OI.CURVES[doc[tag]["curve_id"]]
+    ipk = OI.parse_ipk(_ipk(doc[tag]["issuer"]), C)
+    base = bytes.fromhex(next(c for c in doc[tag]["cases"] if c["name"] == "honest_0")["identity"])
+    outer = OI.pb_fields(base)
+    proof = OI.pb_fields(OI._pb_bytes(outer, 4))
+    rng = random.Random(128)
+
+    def with_nyms(points):
+        """the identity with the points of fields 18 / 19 replaced (their responses kept)"""
+        p = b""
+        for f, wt, v in proof:
+            assert wt == 2 or f == 16
+            if f in points:
+                x, y = points[f]
+                ecp = OI.pb_bytes_field(1, x.to_bytes(32, "big")) + OI.pb_bytes_field(2, y.to_bytes(32, "big"))
+                v = OI.pb_bytes_field(1, ecp) + OI.pb_bytes_field(2, OI._pb_bytes(OI.pb_fields(v), 2))
+            p += OI.pb_bytes_field(f, v) if wt == 2 else REF.ID._varint_field(f, v)
+        return b"".join(OI.pb_bytes_field(f, p if f == 4 else v) for f, _, v in outer)
+
+    items = []
+    for le, lr in zip(ATTR_LENS, reversed(ATTR_LENS)):
+        eid, rh = rng.randbytes(le), rng.randbytes(lr)
+        q_eid, q_rh = rng.randrange(1, C.r), rng.randrange(1, C.r)
+        pts = {18: C.add(C.mul(ipk["h_attrs"][2], C.hash_to_zr(eid)), C.mul(ipk["h_rand"], q_eid)),
+               19: C.add(C.mul(ipk["h_attrs"][3], C.hash_to_zr(rh)), C.mul(ipk["h_rand"], q_rh))}
+        ident = with_nyms(pts)
+        items.append((ident, eid, q_eid, rh, q_rh))
+        flip = lambda b: b[:-1] + bytes([b[-1] ^ 1])  # noqa: E731
+        items.append((ident, flip(eid), q_eid, rh, q_rh) if le >= lr else (ident, eid, q_eid, flip(rh), q_rh))
+    want = [REF.audit_match(ipk, C, *it) for it in items]
+    assert want[0::2] == [None] * len(ATTR_LENS)
+    assert set(want[1::2]) == {REF.E_EID_MISMATCH, REF.E_RH_MISMATCH}
+    st = verifiers[tag].audit_match_batch([it[0] for it in items], [it[1] for it in items],
+                                          [it[2].to_bytes(32, "big") for it in items], [it[3] for it in items],
+                                          [it[4].to_bytes(32, "big") for it in items])
+    assert _messages(st) == want
+
+
 def test_wrong_issuer(doc):
     """charlie's honest BN254 identities under the tokengen issuer key: other bases, so
     the first commitment already differs"""

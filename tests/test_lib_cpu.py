@@ -82,6 +82,8 @@ def test_idemix_parse_check(tmp_path):
     out = subprocess.run([exe, str(inp)], capture_output=True, text=True, timeout=120)
     assert out.returncode == 0, out.stdout + out.stderr
     assert "idemix_parse_check: ok" in out.stdout
+    # the nym items' staging (pack_nym_item): 3 key forms x 7 messages on BN254, 4 x 7 on FP256BN
+    assert "idemix_parse_check: pack 49 cases" in out.stdout
 
 
 def test_status_strings():

@@ -97,6 +97,25 @@ def test_nym_proto_writer():
             assert O.decode_nym_sig(raw, C_) == q
 
 
+def test_padded_stream_words_against_sha256():
+    # the nym and audit kernels' padded_word / padded_blocks on the host: every tail length
+    # 0..200 behind no prefix (FP256BN, audit) and behind the 164-byte BN254 prefix, so every
+    # residue mod 64 of the total, the 55/56 and 63/0 edges among them, several times over
+    import hashlib
+    rng = random.Random(164)
+    cases = [(rng.randbytes(pre), rng.randbytes(ln)) for pre in (0, 164) for ln in range(201)]
+    out = run(["pad %s %s" % (p.hex() or "-", t.hex() or "-") for p, t in cases])
+    for (p, t), got in zip(cases, out):
+        assert got == hashlib.sha256(p + t).hexdigest(), (len(p), len(t))
+
+
+def test_padded_block_count_does_not_wrap():
+    # the longest stream the API takes: (len + 72) / 64 wraps in 32 bits there
+    lens = [0, 55, 56, 63, 64, 119, 120, 0xFFFFFF00 + 166, 0xFFFFFFFF]
+    out = run(["blocks %08x" % n for n in lens])
+    assert [int(o, 16) for o in out] == [(n + 9 + 63) // 64 for n in lens]
+
+
 def test_sign_entry_points_argument_errors():
     from fts_gpu import _lib as L
     lib = L.lib

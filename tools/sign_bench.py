@@ -10,7 +10,8 @@ min and median over the timed rounds.  Every message is distinct, so every nonce
 table row gathered is (repeated scalars would gather the same rows from cache, DESIGN.md §0);
 keys cycle through 64 (ECDSA) / 16 (nym) distinct ones, which the signing kernels cannot
 tell from 65,536.  What was timed is then verified on the device (every verdict FTS_OK),
-which also gives k_ecdsa_verify / k_nym_verify / k_nym_verify_fbn on the same items.
+which also gives k_ecdsa_verify / k_nym_verify / k_nym_verify_fbn on the same items (the nym labels
+name k_nym_sign<BnCurve> / k_nym_sign<FbnCurve>, the BN254 k_nym_verify and k_nym_verify<FbnCurve>).
 
 CPU column: `openssl speed ecdsap256` sign/s of one core times 16 (the cores a caller of
 this library has), if an openssl binary exists; otherwise none is recorded.
