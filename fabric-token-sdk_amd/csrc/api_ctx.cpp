@@ -523,6 +523,8 @@ const char* fts_status_str(int32_t s) {
     case FTS_E_CRED_MALFORMED: return "credential malformed";
     case FTS_E_CRED_B: return "b-value from credential does not match the attribute values";
     case FTS_E_CRED_PAIRING: return "credential is not cryptographically valid";
+    case FTS_E_CREDREQ_MALFORMED: return "one of the proof values is undefined";
+    case FTS_E_CREDREQ_INVALID: return "zero knowledge proof is invalid";
     default: return "unknown status";
   }
 }

@@ -132,7 +132,11 @@ struct fts_idemix_idv {
   int curve = 1;
   DevBuf d_tables;  // HSk, HRand, HAttrs[0..3], g1
   DevBuf d_lines;   // lines of W, then of g2
-  DevBuf d_hash;    // ipk.Hash as 8 big-endian words
+  DevBuf d_hash;    // ipk.Hash as 8 big-endian words, then HSk as X || Y (16): the credential-request transcript
+  // BarG1 then BarG2 of the key as X || Y (an issuer handle checks its secret against them)
+  uint8_t bar[128];
+  bool has_bar = false;
+  CredReqState* creq = nullptr;  // slots of the credential-request calls (api_credissue.cpp)
   SlotRing<IdvSlot, IDV_NSLOT> ring;  // its lock also guards last_* and g2_seen
   float last_ms[2] = {0.f, 0.f};
   // batch pairing check (k_idv_bp_*; FTS_IDV_BATCH=0 pairs every identity, the A/B
@@ -152,13 +156,18 @@ struct fts_idemix_idv {
   float aud_ms = 0.f;  // under aud.mu
   ~fts_idemix_idv() {
     if (device >= 0) (void)hipSetDevice(device);
+    credreq_state_free(creq);
   }
 };
 
-// what a credential handle borrows from its identity verifier (api_idgen.cpp)
+// what a credential handle borrows from its identity verifier (api_idgen.cpp), and an issuer
+// handle and the credential-request calls (api_credissue.cpp)
 namespace idv {
 IdvView idv_view(const fts_idemix_idv* k) {
   return IdvView{k->device, k->curve, k->d_tables.as<uint32_t>(), k->d_hash.as<uint32_t>()};
+}
+IssuerView idv_issuer_view(const fts_idemix_idv* k) {
+  return IssuerView{idv_view(k), k->creq, k->has_bar ? k->bar : nullptr};
 }
 }  // namespace idv
 
@@ -456,16 +465,18 @@ int fts_idemix_idv_create(int device, const uint8_t* ipk, size_t ipk_len, int cu
   if (const char* e = getenv("FTS_IDV_BATCH")) k->batch = atoi(e) != 0;
   if (hipSetDevice(device) != hipSuccess) return FTS_API_EDEVICE;
   uint8_t h32[32];
-  uint32_t hw[8];
+  uint32_t hw[24];  // ipk.Hash, then HSk as X || Y
   ipk_hash32(f, h32);
   be_words(h32, hw);
+  be_words(raw[B_HSK], hw + 8), be_words(raw[B_HSK] + 32, hw + 16);
+  k->has_bar = ecp_xy(f.bar_g1, k->bar, false) && ecp_xy(f.bar_g2, k->bar + 64, false);
   const size_t wpb = bn ? fb_words_per_base() : fbn_words_per_base();
   const size_t nl = line_words(bn);
   Stream s0;
   DevBuf bases_buf, scr_buf, w_buf, ok_buf;
   const size_t scr_b = bn ? table_build_scratch_bytes(NB) : (size_t)NB * 16 * 4;
   bool ok = s0.create() == hipSuccess && k->d_tables.reserve((size_t)NB * wpb * 4) &&
-            k->d_lines.reserve(2 * nl * 4) && k->d_hash.reserve(32) && bases_buf.reserve(sizeof bases) &&
+            k->d_lines.reserve(2 * nl * 4) && k->d_hash.reserve(sizeof hw) && bases_buf.reserve(sizeof bases) &&
             scr_buf.reserve(scr_b) && w_buf.reserve(128) && ok_buf.reserve(64);
   uint32_t* const d_tables = k->d_tables.as<uint32_t>();
   uint32_t* const d_lines = k->d_lines.as<uint32_t>();
@@ -474,7 +485,7 @@ int fts_idemix_idv_create(int device, const uint8_t* ipk, size_t ipk_len, int cu
   int32_t* const d_ok = ok_buf.as<int32_t>();
   ok = ok && hipMemcpyAsync(d_bases, bases, sizeof bases, hipMemcpyHostToDevice, s0) == hipSuccess &&
        hipMemcpyAsync(d_w, wraw, 128, hipMemcpyHostToDevice, s0) == hipSuccess &&
-       hipMemcpyAsync(k->d_hash.p, hw, 32, hipMemcpyHostToDevice, s0) == hipSuccess &&
+       hipMemcpyAsync(k->d_hash.p, hw, sizeof hw, hipMemcpyHostToDevice, s0) == hipSuccess &&
        hipMemsetAsync(d_ok, 0, 64, s0) == hipSuccess;
   int32_t hok[NB + 1] = {0};
   if (ok) {
@@ -503,6 +514,7 @@ int fts_idemix_idv_create(int device, const uint8_t* ipk, size_t ipk_len, int cu
     ok = ok && S.stream.create() == hipSuccess;
     for (auto& e : S.ev) ok = ok && e.create() == hipSuccess;
   }
+  ok = ok && (k->creq = credreq_state_new()) != nullptr;
   if (!ok) return FTS_API_EDEVICE;
   *out = k.release();
   return FTS_API_OK;

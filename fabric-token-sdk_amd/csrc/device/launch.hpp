@@ -228,4 +228,44 @@ struct CredChain {
 template <class CV>
 void launch_cred_prep(const CredChain& c);
 size_t cred_scratch_words(size_t n);
+
+// ---- idemix_credissue_<cv>.hip (device/credissue_kernels.hpp): credential requests made and
+// checked, credentials issued
+// per request checked (CI_REC_WORDS, canonical limbs): proof_c as sent (compared), proof_c and
+// proof_s mod r, the nonce as big-endian words, then for an issue S, attrs[0..3], E
+constexpr int CI_R_CCMP = 0, CI_R_CMUL = 8, CI_R_S = 16, CI_R_NONCE = 24, CI_R_BIGS = 32, CI_R_ATTR = 40, CI_R_E = 72;
+constexpr int CI_REC_WORDS = 80, CI_NPROD = 7;
+// per request made: sk, rSk, the nonce as big-endian words; words written back by
+// k_ci_request (Nym c s) and k_ci_sign (A B); transcript bytes per lane (five SHA-256 blocks)
+constexpr int CIQ_REC_WORDS = 24, CI_OUT_WORDS = 32, CI_MSG_BYTES = 320;
+struct CredReqChain {
+  hipStream_t s;
+  hipEvent_t ev_mid;    // an issue: recorded between k_ci_check and k_ci_sign
+  int n;
+  const uint32_t* rec;  // [n][CI_REC_WORDS] (made: [n][CIQ_REC_WORDS])
+  const uint8_t* pts;   // [n][64] Nym, X || Y
+  uint32_t* scr;        // credissue_scratch_words(n)
+  uint8_t* msg;         // [CI_MSG_BYTES][n]
+  uint32_t* out;        // [n][CI_OUT_WORDS]
+  int32_t* st;
+  const uint32_t *tables, *hk, *isk;  // the issuer's seven; ipk.Hash then HSk (X || Y), big-endian words; the secret
+};
+template <class CV>
+void launch_credreq_make(const CredReqChain& c);
+template <class CV>
+hipError_t launch_credissue(const CredReqChain& c, bool issue);
+template <class CV>
+void launch_credissue_key(const uint8_t* bar, const uint32_t* isk, int32_t* ok, hipStream_t s);
+size_t credissue_scratch_words(size_t n);
+// api_idemix.cpp / api_credissue.cpp: the slots of the credential-request calls that run on a
+// verifier's handle, and what an issuer handle borrows from it
+struct CredReqState;
+CredReqState* credreq_state_new();  // nullptr: a stream or an event could not be created
+void credreq_state_free(CredReqState* s);
+struct IssuerView {
+  IdvView v;
+  CredReqState* rq;
+  const uint8_t* bar;  // BarG1 then BarG2 of the key as X || Y (128 bytes); nullptr: the key carries none
+};
+IssuerView idv_issuer_view(const ::fts_idemix_idv* k);
 }  // namespace idv

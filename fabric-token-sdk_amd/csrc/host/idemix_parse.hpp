@@ -368,11 +368,12 @@ inline int32_t parse_audit_identity(const uint8_t* id, size_t len, bool bn, uint
   return FTS_OK;
 }
 
-// IssuerPublicKey: 2 h_sk, 3 h_rand, 4 h_attrs (repeated ECP), 5 w (ECP2), 10 hash;
+// IssuerPublicKey: 2 h_sk, 3 h_rand, 4 h_attrs (repeated ECP), 5 w (ECP2), 6 bar_g1, 7 bar_g2
+// (ECP; an issuer handle checks its secret against them), 10 hash;
 // a field with another wire type is ignored.  false: proto.Unmarshal fails.  Each
 // creator applies its own acceptance rule to the spans.
 struct IpkFields {
-  Span h_sk, h_rand, h_attrs[4], w, hash;
+  Span h_sk, h_rand, h_attrs[4], w, bar_g1, bar_g2, hash;
   size_t n_attrs = 0;  // occurrences of field 4 (the first four are kept)
 };
 inline bool parse_ipk(const uint8_t* ipk, size_t len, IpkFields& k) {
@@ -386,6 +387,8 @@ inline bool parse_ipk(const uint8_t* ipk, size_t len, IpkFields& k) {
     if (d.f == 3) k.h_rand = s;
     if (d.f == 4 && k.n_attrs++ < 4) k.h_attrs[k.n_attrs - 1] = s;
     if (d.f == 5) k.w = s;
+    if (d.f == 6) k.bar_g1 = s;
+    if (d.f == 7) k.bar_g2 = s;
     if (d.f == 10) k.hash = s;
   }
   return true;

@@ -50,9 +50,13 @@ FTS_E_SIGN_BADKEY = 34
 FTS_E_CRED_MALFORMED = 36  # 35 stays unassigned ("unknown status")
 FTS_E_CRED_B = 37
 FTS_E_CRED_PAIRING = 38
+FTS_E_CREDREQ_MALFORMED = 40  # 39 stays unassigned, as 35 does
+FTS_E_CREDREQ_INVALID = 41
 # signing (include/fts_gpu.h)
 FTS_ECDSA_SIG_MAX = 72
 FTS_NYM_SIG_LEN = 136
+FTS_IDEMIX_CRED_REQUEST_LEN = 172
+FTS_IDEMIX_CREDENTIAL_LEN = 344
 FTS_NONCE_RFC6979 = 0
 FTS_NONCE_HEDGED = 1
 # mathlib CurveID of idemix issuer keys
@@ -90,6 +94,10 @@ EXPORTED = [
     "fts_debug_idemix_identity_draws", "fts_debug_idemix_identity_write",
     "fts_debug_table_entries",
     "fts_idemix_cred_verify_batch", "fts_idemix_cred_verify_last_timings", "fts_idemix_cred_verify_last_stats",
+    "fts_idemix_cred_request_batch", "fts_idemix_cred_request_verify_batch", "fts_idemix_cred_request_last_timings",
+    "fts_idemix_issuer_create", "fts_idemix_issuer_destroy", "fts_idemix_cred_issue_batch",
+    "fts_idemix_cred_issue_last_timings", "fts_debug_idemix_cred_issue_draws", "fts_debug_idemix_credreq_parse",
+    "fts_debug_idemix_credreq_write", "fts_debug_idemix_credential_write",
 ]
 # fts_idemix_identity_len, the one entry that returns a size_t, is bound below and not listed
 # here: this list is compared with the header's functions that return int, void or a string
@@ -158,6 +166,14 @@ class AuditItem(C.Structure):
 
 class CredItem(C.Structure):
     _fields_ = [("cred", C.c_void_p), ("cred_len", C.c_size_t), ("sk32", C.c_void_p)]
+
+
+class CredReqItem(C.Structure):
+    _fields_ = [("req", C.c_void_p), ("req_len", C.c_size_t)]
+
+
+class CredIssueItem(C.Structure):  # fts_idemix_issue_item (IssueItem is the zkatdlog issue action's)
+    _fields_ = [("req", C.c_void_p), ("req_len", C.c_size_t), ("attrs4x32", C.c_void_p)]
 
 
 class ActionWitness(C.Structure):
@@ -296,6 +312,17 @@ def _load():
         "fts_idemix_identity_generate_last_timings": ([P, C.POINTER(C.c_float), C.POINTER(C.c_double)], C.c_int),
         "fts_debug_idemix_identity_draws": ([C.c_int, C.c_uint64, C.c_uint64, P], C.c_int),
         "fts_debug_idemix_identity_write": ([C.c_int, U8P, U8P, U8P, U8P, C.c_uint64, P, S, C.POINTER(S)], C.c_int),
+        "fts_idemix_cred_request_batch": ([P, S, P, P, C.c_uint64, P, S, P, I32P], C.c_int),
+        "fts_idemix_cred_request_verify_batch": ([P, S, C.POINTER(CredReqItem), I32P], C.c_int),
+        "fts_idemix_cred_request_last_timings": ([P, C.POINTER(C.c_float)], C.c_int),
+        "fts_idemix_issuer_create": ([P, U8P, C.POINTER(P)], C.c_int),
+        "fts_idemix_issuer_destroy": ([P], None),
+        "fts_idemix_cred_issue_batch": ([P, S, C.POINTER(CredIssueItem), C.c_uint64, P, S, P, I32P], C.c_int),
+        "fts_idemix_cred_issue_last_timings": ([P, C.POINTER(C.c_float), C.POINTER(C.c_double)], C.c_int),
+        "fts_debug_idemix_cred_issue_draws": ([C.c_int, C.c_uint64, C.c_uint64, U8P, P], C.c_int),
+        "fts_debug_idemix_credreq_parse": ([C.c_int, P, S, I32P, P], C.c_int),
+        "fts_debug_idemix_credreq_write": ([U8P, U8P, U8P, U8P, P], C.c_int),
+        "fts_debug_idemix_credential_write": ([U8P, U8P, U8P, U8P, U8P, P], C.c_int),
     }
     for name, (args, res) in sig.items():
         try:

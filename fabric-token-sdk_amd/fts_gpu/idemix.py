@@ -19,6 +19,12 @@ them; ``Credential(verifier, cred, sk).generate(n)`` produces them on the device
 ``IdentityVerifier.verify_credentials(creds, sks)`` / ``VerifyCredential(cred, sk)`` check
 credentials as NewKeyManager does, pairing equation included (km.go:117-133).
 
+Enrolment: ``IdentityVerifier.make_cred_requests(sks, nonces)`` is the wallet's
+NewCredRequest, ``IdentityVerifier.verify_cred_requests(reqs)`` CredRequest.Check, and
+``Issuer(verifier, isk).issue(reqs, attrs)`` checks each request and issues its credential
+(NewCredential), so that request -> credential -> ``Credential`` -> identities -> verified
+identities runs on the device end to end.
+
 The issuer key is the idemix IssuerPublicKey proto a zkatdlog PublicParams
 carries, on BN254 (the tokengen key of zkatdlog_pp.json) or FP256BN_AMCL (the
 validator's test keys).  There is no CPU fallback: every verdict comes from
@@ -37,6 +43,8 @@ from ._lib import (FTS_E_AUDIT_MALFORMED, FTS_E_AUDIT_NO_EIDNYM, FTS_E_AUDIT_EID
 from ._lib import FTS_CURVE_BN254, FTS_CURVE_FP256BN_AMCL  # noqa: F401
 from ._lib import FTS_E_SIGN_BADKEY, FTS_NYM_SIG_LEN  # noqa: F401
 from ._lib import FTS_E_CRED_MALFORMED, FTS_E_CRED_B, FTS_E_CRED_PAIRING  # noqa: F401
+from ._lib import FTS_E_CREDREQ_MALFORMED, FTS_E_CREDREQ_INVALID  # noqa: F401
+from ._lib import FTS_IDEMIX_CRED_REQUEST_LEN, FTS_IDEMIX_CREDENTIAL_LEN  # noqa: F401
 from ._lib import FTS_SEED_OS_RANDOM as OS_RANDOM
 
 
@@ -375,6 +383,51 @@ class IdentityVerifier:
         L.check("fts_idemix_cred_verify_last_stats", L.lib.fts_idemix_cred_verify_last_stats(self.h, out))
         return int(out[0]), int(out[1])
 
+    def make_cred_requests(self, sks, nonces, seed=None, stride=None):
+        """NewCredRequest for n (user secret, issuer nonce) pairs in one device pass
+        (fts_idemix_cred_request_batch).  sks, nonces: ints or 32 big-endian bytes; seed None:
+        the secure source, else test-only (item i equals the one-item call at seed + i).
+        -> (requests: CredRequest protos, b"" for a rejected item; int32 status array)"""
+        n = len(sks)
+        if len(nonces) != n:
+            raise ValueError("sks and nonces must have the same length")
+        ln = FTS_IDEMIX_CRED_REQUEST_LEN
+        stride = ln if stride is None else int(stride)
+        st = np.zeros(n, dtype=np.int32)
+        skb = np.frombuffer(b"".join(_z32(v) for v in sks) or b"\0", dtype=np.uint8)
+        nb = np.frombuffer(b"".join(_z32(v) for v in nonces) or b"\0", dtype=np.uint8)
+        out = np.zeros(max(1, n * stride), dtype=np.uint8)
+        lens = np.zeros(max(1, n), dtype=np.uint32)
+        sd = OS_RANDOM if seed is None else int(seed) & ((1 << 64) - 1)
+        L.check("fts_idemix_cred_request_batch",
+                L.lib.fts_idemix_cred_request_batch(self.h, n, skb.ctypes.data, nb.ctypes.data, sd, out.ctypes.data,
+                                                    stride, lens.ctypes.data, st.ctypes.data_as(C.POINTER(C.c_int32))))
+        raw = out.tobytes()
+        self.last_request_buffer = raw[:n * stride]  # rejected items: zeros
+        return [raw[i * stride:i * stride + int(lens[i])] for i in range(n)], st
+
+    def verify_cred_requests(self, reqs):
+        """CredRequest.Check for n requests in one device pass (fts_idemix_cred_request_verify_batch;
+        None is a NULL pointer) -> int32 status array (FTS_OK or FTS_E_CREDREQ_*)"""
+        n = len(reqs)
+        st = np.zeros(n, dtype=np.int32)
+        if n == 0:
+            return st
+        keep = [None if r is None else bytes(r) for r in reqs]
+        items = (L.CredReqItem * n)()
+        for i, r in enumerate(keep):
+            items[i].req = None if r is None else C.cast(C.c_char_p(r), C.c_void_p)
+            items[i].req_len = len(r or b"")
+        L.check("fts_idemix_cred_request_verify_batch",
+                L.lib.fts_idemix_cred_request_verify_batch(self.h, n, items, st.ctypes.data_as(C.POINTER(C.c_int32))))
+        return st
+
+    def last_cred_request_kernel_ms(self):
+        """HIP-event ms of (the last make_cred_requests, the last verify_cred_requests)"""
+        ms = (C.c_float * 2)()
+        L.check("fts_idemix_cred_request_last_timings", L.lib.fts_idemix_cred_request_last_timings(self.h, ms))
+        return float(ms[0]), float(ms[1])
+
     def pairing_debug(self, which, p64, final_exp=True):
         """e(W or g2, P) on the handle's curve, P = X || Y (64 raw BE bytes): 6 Fp2
         coefficients (w^0..w^5) as Montgomery ints"""
@@ -384,6 +437,120 @@ class IdentityVerifier:
         w = list(out)
         val = lambda o: sum(w[o + i] << (32 * i) for i in range(8))  # noqa: E731
         return [(val(16 * k), val(16 * k + 8)) for k in range(6)]
+
+
+def _z32(v):
+    """an int or 32 big-endian bytes -> 32 bytes (an int outside [0, 2^256): all ones, which is
+    above either r)"""
+    if isinstance(v, int):
+        return v.to_bytes(32, "big") if 0 <= v < (1 << 256) else b"\xff" * 32
+    v = bytes(v)
+    if len(v) != 32:
+        raise ValueError("a scalar is an int or 32 big-endian bytes")
+    return v
+
+
+class Issuer:
+    """One idemix issuer secret on the device (fts_idemix_issuer): issue(reqs, attrs) is what n
+    calls of CredRequest.Check and NewCredential do.  Borrows `verifier` (an IdentityVerifier
+    under the issuer's public key), which must stay open while this handle lives.  Raises
+    FtsError (FTS_API_EPP) for isk = 0, isk >= r or a secret that is not the key's."""
+
+    def __init__(self, verifier, isk):
+        self.verifier = verifier
+        self.curve = verifier.curve
+        h = C.c_void_p()
+        L.check("fts_idemix_issuer_create", L.lib.fts_idemix_issuer_create(verifier.h, _z32(isk), C.byref(h)))
+        self.h = h
+
+    def close(self):
+        if getattr(self, "h", None):
+            L.lib.fts_idemix_issuer_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def issue(self, reqs, attrs, seed=None, stride=None):
+        """reqs: n CredRequest protos (None: a NULL pointer); attrs: n lists of four ints or
+        32-byte strings (None: a NULL pointer); seed None: the secure source, else test-only.
+        -> (credentials: Credential protos, b"" for a rejected item; int32 status array:
+        FTS_OK, FTS_E_SIGN_BADKEY or FTS_E_CREDREQ_*)"""
+        n = len(reqs)
+        if len(attrs) != n:
+            raise ValueError("reqs and attrs must have the same length")
+        ln = FTS_IDEMIX_CREDENTIAL_LEN
+        stride = ln if stride is None else int(stride)
+        st = np.zeros(n, dtype=np.int32)
+        keep = []
+        for r, a in zip(reqs, attrs):
+            if a is not None and len(a) != 4:
+                raise ValueError("four attributes per credential")
+            keep.append((None if r is None else bytes(r), None if a is None else b"".join(_z32(v) for v in a)))
+        items = (L.CredIssueItem * max(1, n))()
+        for i, (r, a) in enumerate(keep):
+            items[i].req = None if r is None else C.cast(C.c_char_p(r), C.c_void_p)
+            items[i].req_len = len(r or b"")
+            items[i].attrs4x32 = None if a is None else C.cast(C.c_char_p(a), C.c_void_p)
+        out = np.zeros(max(1, n * stride), dtype=np.uint8)
+        lens = np.zeros(max(1, n), dtype=np.uint32)
+        sd = OS_RANDOM if seed is None else int(seed) & ((1 << 64) - 1)
+        L.check("fts_idemix_cred_issue_batch",
+                L.lib.fts_idemix_cred_issue_batch(self.h, n, items, sd, out.ctypes.data, stride, lens.ctypes.data,
+                                                  st.ctypes.data_as(C.POINTER(C.c_int32))))
+        raw = out.tobytes()
+        self.last_buffer = raw[:n * stride]  # rejected items: zeros
+        return [raw[i * stride:i * stride + int(lens[i])] for i in range(n)], st
+
+    def last_timings(self):
+        """(decode + products + check ms, A = inv B ms, host parse + draws + staging s, host
+        serialisation s) of the last issue"""
+        ms, hs = (C.c_float * 2)(), (C.c_double * 2)()
+        L.check("fts_idemix_cred_issue_last_timings", L.lib.fts_idemix_cred_issue_last_timings(self.h, ms, hs))
+        return float(ms[0]), float(ms[1]), float(hs[0]), float(hs[1])
+
+
+def cred_issue_draws(curve, seed, i, avoid_e=None):
+    """host-only: (E, S) of Issuer.issue's item i at `seed` and rSk of make_cred_requests' item i,
+    as ints; avoid_e: the value r - isk that E is drawn again on"""
+    out = (C.c_uint8 * 96)()
+    L.check("fts_debug_idemix_cred_issue_draws",
+            L.lib.fts_debug_idemix_cred_issue_draws(int(curve), int(seed), int(i),
+                                                    None if avoid_e is None else _z32(avoid_e), out))
+    b = bytes(out)
+    return tuple(int.from_bytes(b[32 * k:32 * k + 32], "big") for k in range(3))
+
+
+def parse_cred_request(curve, req):
+    """host-only: the host's part of CredRequest.Check (fts_debug_idemix_credreq_parse) ->
+    (status, Nym as X || Y, issuer_nonce, proof_c as sent, proof_s mod r)"""
+    st, out = C.c_int32(), (C.c_uint8 * 160)()
+    r = None if req is None else bytes(req)
+    L.check("fts_debug_idemix_credreq_parse",
+            L.lib.fts_debug_idemix_credreq_parse(int(curve), None if r is None else C.cast(C.c_char_p(r), C.c_void_p),
+                                                 len(r or b""), C.byref(st), out))
+    b = bytes(out)
+    return st.value, b[:64], b[64:96], int.from_bytes(b[96:128], "big"), int.from_bytes(b[128:], "big")
+
+
+def write_cred_request(nym_xy, nonce, c, s):
+    """host-only: the CredRequest writer (nym_xy: (x, y) ints)"""
+    out = (C.c_uint8 * FTS_IDEMIX_CRED_REQUEST_LEN)()
+    L.check("fts_debug_idemix_credreq_write",
+            L.lib.fts_debug_idemix_credreq_write(_z32(nym_xy[0]) + _z32(nym_xy[1]), _z32(nonce), _z32(c), _z32(s), out))
+    return bytes(out)
+
+
+def write_credential(a_xy, b_xy, e, s, attrs):
+    """host-only: the Credential writer (a_xy, b_xy: (x, y) ints; four attributes)"""
+    out = (C.c_uint8 * FTS_IDEMIX_CREDENTIAL_LEN)()
+    L.check("fts_debug_idemix_credential_write",
+            L.lib.fts_debug_idemix_credential_write(_z32(a_xy[0]) + _z32(a_xy[1]), _z32(b_xy[0]) + _z32(b_xy[1]),
+                                                    _z32(e), _z32(s), b"".join(_z32(v) for v in attrs), out))
+    return bytes(out)
 
 
 class IdentityError(Exception):

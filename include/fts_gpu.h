@@ -98,7 +98,13 @@ enum fts_status {
   FTS_E_CRED_MALFORMED = 36,     /* NULL or empty input, Credential proto does not parse, attributes other
                                     than four, a scalar >= r, A or B off the curve or the identity */
   FTS_E_CRED_B = 37,             /* "b-value from credential does not match the attribute values" */
-  FTS_E_CRED_PAIRING = 38        /* "credential is not cryptographically valid" */
+  FTS_E_CRED_PAIRING = 38,       /* "credential is not cryptographically valid" */
+  /* idemix credential requests (IBM/idemix CredRequest.Check), in the order checked.  39 stays
+   * unassigned, as 35 does: fts_status_str(39) has been "unknown status", the first code past the table */
+  FTS_E_CREDREQ_MALFORMED = 40,  /* "one of the proof values is undefined": NULL or empty input, the proto
+                                    does not parse, a missing field, a scalar or nonce not of 32 bytes,
+                                    a Nym that does not decode or is the identity */
+  FTS_E_CREDREQ_INVALID = 41     /* "zero knowledge proof is invalid": the challenge differs */
 };
 
 /* ---- API return codes ---- */
@@ -874,6 +880,97 @@ int fts_idemix_cred_verify_last_timings(fts_idemix_idv* idv, float* ms2);
  * with one randomised pairing product each (0 with FTS_IDV_BATCH=0), out2[1] = credentials
  * paired one by one. */
 int fts_idemix_cred_verify_last_stats(fts_idemix_idv* idv, uint32_t* out2);
+
+/* ---- idemix enrolment on the device: credential requests and issuance ----
+ * The user's NewCredRequest and the issuer's CredRequest.Check and NewCredential (IBM/idemix
+ * bccsp/schemes/dlog/crypto credrequest.go, credential.go; the reference reaches them through
+ * idemixgen and its CA).  With C the curve of the handle's issuer key, points as G1.Bytes() and
+ * scalars as 32 B big-endian:
+ *   request  Nym = HSk sk; t = HSk rSk;
+ *            c = HashToZr("credRequest" || t || HSk || Nym || IssuerNonce || ipk.Hash); s = rSk + c sk
+ *            -> CredRequest{1 nym: ECP{1 x, 2 y}, 2 issuer_nonce, 3 proof_c, 4 proof_s}
+ *   check    t = HSk s - Nym c; accept iff c == HashToZr(the same bytes), as integers
+ *   issue    the check; B = g1 + Nym + HRand S + sum HAttrs[i] attrs[i]; A = B (isk + E)^-1
+ *            -> Credential{1 a, 2 b, 3 e, 4 s, 5 attrs x 4}, what fts_idemix_cred_verify_batch
+ *            and fts_idemix_cred_create take
+ * UNPINNED: the reference holds no credential-request vector, so the label "credRequest" and
+ * the field order of the transcript are restated from the published idemix code.  The
+ * credential equation is pinned: an issued credential is accepted by Credential.Ver, which the
+ * reference's signer configs pin and fts_idemix_cred_verify_batch runs.
+ * Both protos have one fixed length on both curves. */
+#define FTS_IDEMIX_CRED_REQUEST_LEN 172
+#define FTS_IDEMIX_CREDENTIAL_LEN 344
+/* The wallet's side, on the verifier's handle (it needs HSk's table and ipk.Hash only).
+ * sk32, nonce32: n x 32 B (the user secrets, the issuer's nonces).  Item i draws rSk from
+ * RngSource(seed).at(i) (`seed` + i, tests only; FTS_SEED_OS_RANDOM: the secure source), uniform
+ * below r by rejection, on the host pool.  out + i * stride <- the request
+ * (FTS_IDEMIX_CRED_REQUEST_LEN bytes), len[i] <- its length.  status[i] <- FTS_OK |
+ * FTS_E_SIGN_BADKEY (sk >= r, or a NULL sk32 or nonce32: zero bytes, len[i] = 0, the other items
+ * are not affected).  FTS_API_ESIZE, before a byte is written, for a stride below the length;
+ * n = 0 is FTS_API_OK; FTS_API_EINVAL for a NULL handle or output array or n > 2^22.  Thread-
+ * safe (three slots per handle, shared with the request verifier; tiles of 16,384).  sk and rSk
+ * are wiped from the slot on every way out.  Not hardened against timing side channels. */
+int fts_idemix_cred_request_batch(fts_idemix_idv* idv, size_t n, const uint8_t* sk32, const uint8_t* nonce32,
+                                  uint64_t seed, uint8_t* out, size_t stride, uint32_t* len, int32_t* status);
+/* CredRequest.Check alone: holds no secret.  status[i] <- FTS_OK or
+ *   FTS_E_CREDREQ_MALFORMED  a NULL or empty input; a proto that does not parse; a missing field;
+ *                            proof_c, proof_s or issuer_nonce not of 32 bytes; a Nym that does not
+ *                            decode on the handle's curve or is the identity
+ *   FTS_E_CREDREQ_INVALID    the challenge differs
+ * proof_s >= r is used mod r; proof_c >= r can never equal the recomputed challenge and is
+ * FTS_E_CREDREQ_INVALID (the conventions of fts_nym_verify_batch).  Divergences from the
+ * reference: a nonce of another length, and the identity as Nym on BN254. */
+typedef struct {
+  const uint8_t* req;
+  size_t req_len;
+} fts_idemix_credreq_item;
+int fts_idemix_cred_request_verify_batch(fts_idemix_idv* idv, size_t n, const fts_idemix_credreq_item* items,
+                                         int32_t* status);
+/* HIP-event durations (ms) of the handle's last request batch ([0], k_ci_request) and last
+ * request-verification batch ([1], decode, the two products and the check), summed over tiles. */
+int fts_idemix_cred_request_last_timings(fts_idemix_idv* idv, float* ms2);
+
+/* One handle per issuer secret.  Borrows idv's device, its seven tables and ipk.Hash, as
+ * fts_idemix_cred does: destroy it before idv.  FTS_API_EPP for isk = 0, isk >= r, a key
+ * without BarG1 / BarG2 or BarG2 != isk BarG1 (a G1 check on the device; the key's own proof of
+ * knowledge, not checked here, ties W to it).  isk is zeroed on the device and the host before
+ * it is freed, on destroy and on every error path. */
+typedef struct fts_idemix_issuer fts_idemix_issuer;
+int fts_idemix_issuer_create(fts_idemix_idv* idv, const uint8_t* isk32, fts_idemix_issuer** out);
+void fts_idemix_issuer_destroy(fts_idemix_issuer* issuer);
+/* Check each request, then issue.  attrs4x32: the four attribute values, 32 B big-endian each.
+ * Item i draws E, then S from RngSource(seed).at(i) on the host pool; an E with E + isk = 0
+ * mod r is drawn again.  creds + i * stride <- the credential (FTS_IDEMIX_CREDENTIAL_LEN bytes),
+ * cred_len[i] <- its length.  status[i] <- FTS_OK | FTS_E_SIGN_BADKEY (an attribute >= r or NULL
+ * attrs4x32) | FTS_E_CREDREQ_MALFORMED | FTS_E_CREDREQ_INVALID; a rejected item writes zeros and
+ * cred_len[i] = 0 and moves no other item's draws or bytes.  FTS_API_ESIZE, before a byte is
+ * written, for a stride below the length; n = 0 is FTS_API_OK; FTS_API_EINVAL for a NULL handle
+ * or array or n > 2^22.  Thread-safe: three slots per handle; a call above 16,384 items runs in
+ * tiles of that size.  (isk + E)^-1, E and S are wiped from the slot on every way out.  Not
+ * hardened against timing side channels (table indices and branches depend on secrets). */
+typedef struct {
+  const uint8_t* req;
+  size_t req_len;
+  const uint8_t* attrs4x32;
+} fts_idemix_issue_item;
+int fts_idemix_cred_issue_batch(fts_idemix_issuer* issuer, size_t n, const fts_idemix_issue_item* items,
+                                uint64_t seed, uint8_t* creds, size_t stride, uint32_t* cred_len, int32_t* status);
+/* The last issue batch: ms2[0] decode, the seven products and the check, ms2[1] A = inv B
+ * (HIP events); host_s2 (optional): [0] parsing, draws and staging, [1] serialisation. */
+int fts_idemix_cred_issue_last_timings(fts_idemix_issuer* issuer, float* ms2, double* host_s2);
+/* Host-only (tests): item i's draws at `seed` (not FTS_SEED_OS_RANDOM), 32 B big-endian each:
+ * E, S of fts_idemix_cred_issue_batch, then rSk of fts_idemix_cred_request_batch.
+ * avoid_e32 (optional): the value r - isk that E is drawn again on. */
+int fts_debug_idemix_cred_issue_draws(int curve_id, uint64_t seed, uint64_t i, const uint8_t* avoid_e32,
+                                      uint8_t* out3x32);
+/* Host-only (tests): the parser and the writers of host/credreq_write.hpp.  _parse: status of
+ * the host's part of the check, out160 <- Nym (X || Y), issuer_nonce, proof_c as sent, proof_s
+ * mod r.  The writers fill exactly FTS_IDEMIX_CRED_REQUEST_LEN / FTS_IDEMIX_CREDENTIAL_LEN bytes. */
+int fts_debug_idemix_credreq_parse(int curve_id, const uint8_t* req, size_t req_len, int32_t* status, uint8_t* out160);
+int fts_debug_idemix_credreq_write(const uint8_t* nym64, const uint8_t* nonce32, const uint8_t* c32, const uint8_t* s32,
+                                   uint8_t* out);
+int fts_debug_idemix_credential_write(const uint8_t* a64, const uint8_t* b64, const uint8_t* e32, const uint8_t* s32,
+                                      const uint8_t* attrs4x32, uint8_t* out);
 
 #ifdef __cplusplus
 }
