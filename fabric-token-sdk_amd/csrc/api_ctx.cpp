@@ -525,6 +525,9 @@ const char* fts_status_str(int32_t s) {
     case FTS_E_CRED_PAIRING: return "credential is not cryptographically valid";
     case FTS_E_CREDREQ_MALFORMED: return "one of the proof values is undefined";
     case FTS_E_CREDREQ_INVALID: return "zero knowledge proof is invalid";
+    case FTS_E_IPK_MALFORMED: return "issuer public key malformed";
+    case FTS_E_IPK_UNDEFINED: return "some part of the public key is undefined";
+    case FTS_E_IPK_PROOF: return "zero knowledge proof in public key invalid";
     default: return "unknown status";
   }
 }

@@ -268,4 +268,27 @@ struct IssuerView {
   const uint8_t* bar;  // BarG1 then BarG2 of the key as X || Y (128 bytes); nullptr: the key carries none
 };
 IssuerView idv_issuer_view(const ::fts_idemix_idv* k);
+
+// ---- idemix_ipk_<cv>.hip (device/ipk_kernels.hpp): issuer keys checked and generated
+// per key checked (IPK_REC_WORDS): ProofC as sent (compared), ProofS mod r, -ProofC mod r
+// (canonical limbs), then where the key's HSk, HRand and HAttrs start in the G1 list and how many
+constexpr int IPK_R_CCMP = 0, IPK_R_A = 8, IPK_R_B = 16, IPK_R_OFF = 24, IPK_R_CNT = 25, IPK_REC_WORDS = 28;
+// per key generated: the draws isk, HSk, HRand, HAttrs[0..3], BarG1, r (canonical limbs); the
+// points k_ipk_points writes (the first seven draws' after isk, BarG2, t2); transcript bytes
+// per lane (ten SHA-256 blocks)
+constexpr int IPK_ND = 9, IPK_D_ISK = 0, IPK_D_BAR = 7, IPK_D_R = 8, IPK_NPT = 9, IPK_MSG_BYTES = 640;
+struct IpkChain {
+  hipStream_t s;
+  int n;
+  const uint32_t* rec;  // check: [n][IPK_REC_WORDS]; keygen: [n][IPK_ND][8]
+  const uint8_t *g1, *bar, *w;  // check: the G1 list; [n][128] BarG1 BarG2; [n][128] W
+  const uint8_t* g2;    // the generator's 128 bytes, proto order
+  uint32_t *wdec, *t1, *t2, *out;  // [n][32]; [n][32] (keygen [2][n][32]); [n][16] (keygen [n][IPK_NPT][16]); [n][16]
+  uint8_t* msg;         // [IPK_MSG_BYTES][n]
+  int32_t* st;
+};
+template <class CV>
+void launch_ipk_check(const IpkChain& c);
+template <class CV>
+void launch_ipk_keygen(const IpkChain& c);
 }  // namespace idv

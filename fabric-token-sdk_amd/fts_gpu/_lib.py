@@ -52,11 +52,15 @@ FTS_E_CRED_B = 37
 FTS_E_CRED_PAIRING = 38
 FTS_E_CREDREQ_MALFORMED = 40  # 39 stays unassigned, as 35 does
 FTS_E_CREDREQ_INVALID = 41
+FTS_E_IPK_MALFORMED = 43  # 42 stays unassigned, as 35 and 39 do
+FTS_E_IPK_UNDEFINED = 44
+FTS_E_IPK_PROOF = 45
 # signing (include/fts_gpu.h)
 FTS_ECDSA_SIG_MAX = 72
 FTS_NYM_SIG_LEN = 136
 FTS_IDEMIX_CRED_REQUEST_LEN = 172
 FTS_IDEMIX_CREDENTIAL_LEN = 344
+FTS_IDEMIX_IPK_LEN = 843
 FTS_NONCE_RFC6979 = 0
 FTS_NONCE_HEDGED = 1
 # mathlib CurveID of idemix issuer keys
@@ -98,6 +102,8 @@ EXPORTED = [
     "fts_idemix_issuer_create", "fts_idemix_issuer_destroy", "fts_idemix_cred_issue_batch",
     "fts_idemix_cred_issue_last_timings", "fts_debug_idemix_cred_issue_draws", "fts_debug_idemix_credreq_parse",
     "fts_debug_idemix_credreq_write", "fts_debug_idemix_credential_write",
+    "fts_idemix_ipk_check_batch", "fts_idemix_issuer_keygen_batch", "fts_idemix_issuer_key_last_timings",
+    "fts_debug_idemix_keygen_draws", "fts_debug_idemix_ipk_parse",
 ]
 # fts_idemix_identity_len, the one entry that returns a size_t, is bound below and not listed
 # here: this list is compared with the header's functions that return int, void or a string
@@ -323,6 +329,11 @@ def _load():
         "fts_debug_idemix_credreq_parse": ([C.c_int, P, S, I32P, P], C.c_int),
         "fts_debug_idemix_credreq_write": ([U8P, U8P, U8P, U8P, P], C.c_int),
         "fts_debug_idemix_credential_write": ([U8P, U8P, U8P, U8P, U8P, P], C.c_int),
+        "fts_idemix_ipk_check_batch": ([C.c_int, C.c_int, S, P, P, I32P, P], C.c_int),
+        "fts_idemix_issuer_keygen_batch": ([C.c_int, C.c_int, S, C.c_uint64, P, P, S, P], C.c_int),
+        "fts_idemix_issuer_key_last_timings": ([C.POINTER(C.c_float)], C.c_int),
+        "fts_debug_idemix_keygen_draws": ([C.c_int, C.c_uint64, C.c_uint64, P], C.c_int),
+        "fts_debug_idemix_ipk_parse": ([C.c_int, P, S, I32P, P], C.c_int),
     }
     for name, (args, res) in sig.items():
         try:

@@ -25,6 +25,10 @@ NewCredRequest, ``IdentityVerifier.verify_cred_requests(reqs)`` CredRequest.Chec
 (NewCredential), so that request -> credential -> ``Credential`` -> identities -> verified
 identities runs on the device end to end.
 
+Issuer keys: ``check_issuer_keys(ipks, curve)`` is IssuerPublicKey.Check (the key's proof of
+knowledge of its secret, G2 side included) and ``generate_issuer_keys(n, curve)`` NewIssuerKey,
+so the chain above can start from a key made on the device.
+
 The issuer key is the idemix IssuerPublicKey proto a zkatdlog PublicParams
 carries, on BN254 (the tokengen key of zkatdlog_pp.json) or FP256BN_AMCL (the
 validator's test keys).  There is no CPU fallback: every verdict comes from
@@ -45,6 +49,7 @@ from ._lib import FTS_E_SIGN_BADKEY, FTS_NYM_SIG_LEN  # noqa: F401
 from ._lib import FTS_E_CRED_MALFORMED, FTS_E_CRED_B, FTS_E_CRED_PAIRING  # noqa: F401
 from ._lib import FTS_E_CREDREQ_MALFORMED, FTS_E_CREDREQ_INVALID  # noqa: F401
 from ._lib import FTS_IDEMIX_CRED_REQUEST_LEN, FTS_IDEMIX_CREDENTIAL_LEN  # noqa: F401
+from ._lib import FTS_E_IPK_MALFORMED, FTS_E_IPK_UNDEFINED, FTS_E_IPK_PROOF, FTS_IDEMIX_IPK_LEN  # noqa: F401
 from ._lib import FTS_SEED_OS_RANDOM as OS_RANDOM
 
 
@@ -551,6 +556,85 @@ def write_credential(a_xy, b_xy, e, s, attrs):
             L.lib.fts_debug_idemix_credential_write(_z32(a_xy[0]) + _z32(a_xy[1]), _z32(b_xy[0]) + _z32(b_xy[1]),
                                                     _z32(e), _z32(s), b"".join(_z32(v) for v in attrs), out))
     return bytes(out)
+
+
+class IssuerKeyError(Exception):
+    def __init__(self, msg, status, index):
+        super().__init__(msg)
+        self.status = status
+        self.index = index
+
+
+def check_issuer_keys(ipks, curve, device=0, raise_on_error=False, return_hashes=False):
+    """IssuerPublicKey.Check for a list of IssuerPublicKey protos (None: a NULL pointer) on the
+    device (fts_idemix_ipk_check_batch; no handle).  -> int32 status array: FTS_OK or
+    FTS_E_IPK_MALFORMED / _UNDEFINED / _PROOF; with return_hashes also the n hashes (HashToZr of
+    each key without its hash field, 32 bytes).  raise_on_error: IssuerKeyError for the first
+    bad key, carrying the reference's message.  The handles (IssuerKey, IdentityVerifier, Issuer)
+    do not run this check: a caller that wants the reference's import semantics runs it first."""
+    keep = [None if k is None else bytes(k) for k in ipks]
+    n = len(keep)
+    ptrs = (C.c_void_p * max(1, n))()
+    lens = (C.c_size_t * max(1, n))()
+    for i, k in enumerate(keep):
+        ptrs[i] = None if k is None else C.cast(C.c_char_p(k), C.c_void_p)
+        lens[i] = len(k or b"")
+    st = np.zeros(n, dtype=np.int32)
+    hs = np.zeros(max(1, n * 32), dtype=np.uint8)
+    L.check("fts_idemix_ipk_check_batch",
+            L.lib.fts_idemix_ipk_check_batch(int(device), int(curve), n, ptrs, lens,
+                                             st.ctypes.data_as(C.POINTER(C.c_int32)), hs.ctypes.data))
+    if raise_on_error:
+        for i, s in enumerate(st):
+            if s != FTS_OK:
+                raise IssuerKeyError(L.status_str(s), int(s), i)
+    if return_hashes:
+        raw = hs.tobytes()
+        return st, [raw[32 * i:32 * i + 32] for i in range(n)]
+    return st
+
+
+def generate_issuer_keys(n, curve, seed=None, device=0, stride=None):
+    """NewIssuerKey n times on the device (fts_idemix_issuer_keygen_batch), attribute names OU,
+    Role, EnrollmentID, RevocationHandle.  seed None: the secure source, else test-only (key i
+    draws from seed + i).  -> [(isk as an int, IssuerPublicKey proto)]"""
+    stride = FTS_IDEMIX_IPK_LEN if stride is None else int(stride)
+    isk = np.zeros(max(1, n * 32), dtype=np.uint8)
+    out = np.zeros(max(1, n * stride), dtype=np.uint8)
+    lens = np.zeros(max(1, n), dtype=np.uint32)
+    sd = OS_RANDOM if seed is None else int(seed) & ((1 << 64) - 1)
+    L.check("fts_idemix_issuer_keygen_batch",
+            L.lib.fts_idemix_issuer_keygen_batch(int(device), int(curve), n, sd, isk.ctypes.data, out.ctypes.data,
+                                                 stride, lens.ctypes.data))
+    ib, raw = isk.tobytes(), out.tobytes()
+    return [(int.from_bytes(ib[32 * i:32 * i + 32], "big"), raw[i * stride:i * stride + int(lens[i])])
+            for i in range(n)]
+
+
+def issuer_key_last_kernel_ms():
+    """(HIP-event ms of this process's last check_issuer_keys call, of its last generate_issuer_keys call)"""
+    ms = (C.c_float * 2)()
+    L.check("fts_idemix_issuer_key_last_timings", L.lib.fts_idemix_issuer_key_last_timings(ms))
+    return float(ms[0]), float(ms[1])
+
+
+def keygen_draws(curve, seed, i):
+    """host-only: key i's draws at `seed` as ints, in the order isk, HSk, HRand, HAttrs[0..3],
+    BarG1, r (the nine generate_issuer_keys consumes), then the stream's next value"""
+    out = (C.c_uint8 * 320)()
+    L.check("fts_debug_idemix_keygen_draws", L.lib.fts_debug_idemix_keygen_draws(int(curve), int(seed), int(i), out))
+    b = bytes(out)
+    return [int.from_bytes(b[32 * k:32 * k + 32], "big") for k in range(10)]
+
+
+def parse_issuer_key(curve, ipk):
+    """host-only: the host's part of the check (fts_debug_idemix_ipk_parse) -> (status, hash)"""
+    st, out = C.c_int32(), (C.c_uint8 * 32)()
+    k = None if ipk is None else bytes(ipk)
+    L.check("fts_debug_idemix_ipk_parse",
+            L.lib.fts_debug_idemix_ipk_parse(int(curve), None if k is None else C.cast(C.c_char_p(k), C.c_void_p),
+                                             len(k or b""), C.byref(st), out))
+    return st.value, bytes(out)
 
 
 class IdentityError(Exception):

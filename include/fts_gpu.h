@@ -104,7 +104,15 @@ enum fts_status {
   FTS_E_CREDREQ_MALFORMED = 40,  /* "one of the proof values is undefined": NULL or empty input, the proto
                                     does not parse, a missing field, a scalar or nonce not of 32 bytes,
                                     a Nym that does not decode or is the identity */
-  FTS_E_CREDREQ_INVALID = 41     /* "zero knowledge proof is invalid": the challenge differs */
+  FTS_E_CREDREQ_INVALID = 41,    /* "zero knowledge proof is invalid": the challenge differs */
+  /* idemix issuer public keys (IBM/idemix IssuerPublicKey.Check; fts_idemix_ipk_check_batch).  The
+   * wording of the three messages is restated from the published idemix code.  42 stays
+   * unassigned, as 35 and 39 do: fts_status_str(42) has been "unknown status" */
+  FTS_E_IPK_MALFORMED = 43,      /* NULL or empty input, the proto does not parse, a point that does not
+                                    decode on the curve (W: on the twist), ProofC or ProofS not of 32 bytes */
+  FTS_E_IPK_UNDEFINED = 44,      /* "some part of the public key is undefined": HSk, HRand, W, BarG1, BarG2,
+                                    ProofC or ProofS missing, BarG1 the identity, fewer HAttrs than names */
+  FTS_E_IPK_PROOF = 45           /* "zero knowledge proof in public key invalid": the challenge differs */
 };
 
 /* ---- API return codes ---- */
@@ -933,8 +941,8 @@ int fts_idemix_cred_request_last_timings(fts_idemix_idv* idv, float* ms2);
 /* One handle per issuer secret.  Borrows idv's device, its seven tables and ipk.Hash, as
  * fts_idemix_cred does: destroy it before idv.  FTS_API_EPP for isk = 0, isk >= r, a key
  * without BarG1 / BarG2 or BarG2 != isk BarG1 (a G1 check on the device; the key's own proof of
- * knowledge, not checked here, ties W to it).  isk is zeroed on the device and the host before
- * it is freed, on destroy and on every error path. */
+ * knowledge, not checked here, ties W to it: fts_idemix_ipk_check_batch checks it).  isk is
+ * zeroed on the device and the host before it is freed, on destroy and on every error path. */
 typedef struct fts_idemix_issuer fts_idemix_issuer;
 int fts_idemix_issuer_create(fts_idemix_idv* idv, const uint8_t* isk32, fts_idemix_issuer** out);
 void fts_idemix_issuer_destroy(fts_idemix_issuer* issuer);
@@ -971,6 +979,72 @@ int fts_debug_idemix_credreq_write(const uint8_t* nym64, const uint8_t* nonce32,
                                    uint8_t* out);
 int fts_debug_idemix_credential_write(const uint8_t* a64, const uint8_t* b64, const uint8_t* e32, const uint8_t* s32,
                                       const uint8_t* attrs4x32, uint8_t* out);
+
+/* ---- idemix issuer keys on the device: IssuerPublicKey.Check and NewIssuerKey (IBM/idemix
+ * bccsp/schemes/dlog/crypto issuerkey.go; the reference runs Check whenever it imports a key and
+ * makes keys through idemixgen's CA), on both curves.  The key's proof of knowledge of isk:
+ *   check    t1 = g2 s - W c; t2 = BarG1 s - BarG2 c;
+ *            accept iff c == HashToZr(t1 || t2 || g2 || BarG1 || W || BarG2), as integers
+ *   keygen   W = g2 isk; BarG2 = BarG1 isk; t1 = g2 r; t2 = BarG1 r; c as above; s = r + c isk
+ * G1 points are hashed as G1.Bytes(), G2 points as the four 32-byte coordinates of the ECP2
+ * proto in field order (1, 2, 3, 4) on both curves.  PINNED: the reference's four issuer keys
+ * (two per curve) verify under this reading and under no other coordinate order.
+ *
+ * IssuerPublicKey.Check for n keys, no handle needed.  status[i] <- FTS_OK or
+ *   FTS_E_IPK_MALFORMED  a NULL or empty item; a proto that does not parse; HSk, HRand, an
+ *                        HAttrs, BarG1 or BarG2 that does not decode on the curve, or W that does
+ *                        not (the rules of fts_idemix_idv_create: canonical coordinates of 32
+ *                        bytes, on the curve, the bases not the identity; W on the twist, not
+ *                        the identity and, on BN254, in the subgroup); ProofC or ProofS not of
+ *                        32 bytes.  BarG2 is not one of the bases: on BN254 its identity
+ *                        encoding (64 zero bytes) decodes, as in the reference, its term of t2
+ *                        vanishes and the key ends as FTS_E_IPK_PROOF; on FP256BN x = 0, y = 1
+ *                        is off the curve and the key is malformed
+ *   FTS_E_IPK_UNDEFINED  "some part of the public key is undefined": HSk, HRand, W, BarG1, BarG2,
+ *                        ProofC or ProofS missing; fewer HAttrs than attribute names; BarG1 the
+ *                        identity (BN254: 64 zero bytes; FP256BN: x = 0, y = 1, AMCL's)
+ *   FTS_E_IPK_PROOF      "zero knowledge proof in public key invalid": the challenge differs
+ * in this order on the host (parse, missing parts, lengths), then on the device (HSk, HRand,
+ * HAttrs and BarG1 decode; BarG1 the identity; BarG2 and W decode; the proof).  The wording of
+ * the messages is restated from the published idemix code.  ProofS >= r is used mod r; ProofC
+ * >= r can never equal the recomputed challenge and is FTS_E_IPK_PROOF (the conventions of
+ * fts_idemix_cred_request_verify_batch and fts_nym_verify_batch).  Unlike the handles, the call
+ * does not require four attributes: it checks the key as given.  hash32_out (optional, n x 32
+ * B) <- HashToZr of the key's bytes without field 10 (zeros where the proto does not parse);
+ * the stored hash field is not compared, as with the handles.  An item's defect does not affect
+ * the others.  n = 0 is FTS_API_OK; FTS_API_EINVAL for a NULL array, an unknown curve or n >
+ * 2^22; FTS_API_EDEVICE for a device that does not exist or fails.  Each call owns its stream
+ * and buffers (one lane per key, tiles of 4,096): meant for key import, not for bulk traffic.
+ *
+ * fts_idemix_ipk_create, fts_idemix_idv_create and fts_idemix_issuer_create do not run this
+ * check and keep accepting what they accepted: a caller that wants the reference's import
+ * semantics calls fts_idemix_ipk_check_batch first. */
+int fts_idemix_ipk_check_batch(int device, int curve_id, size_t n, const uint8_t* const* ipk, const size_t* ipk_len,
+                               int32_t* status, uint8_t* hash32_out);
+/* NewIssuerKey with the four attribute names the handles require (OU, Role, EnrollmentID,
+ * RevocationHandle); the key has one fixed length on both curves. */
+#define FTS_IDEMIX_IPK_LEN 843
+/* Key i draws from RngSource(seed).at(i) (`seed` + i, tests only; FTS_SEED_OS_RANDOM: the secure
+ * source), each value uniform in [1, r) by rejection, in this order: isk, HSk, HRand,
+ * HAttrs[0..3], BarG1, r.  On the device: the bases = their draws times g1, W, BarG2, t1, t2, c
+ * and s as above; the host writes fields 1..9 in number order and field 10 = HashToZr of those
+ * bytes.  ipk_out + i * ipk_stride <- the key (FTS_IDEMIX_IPK_LEN bytes), ipk_len[i] <- its
+ * length, isk32_out + 32 i <- isk (big-endian).  FTS_API_ESIZE, before a byte is written, for a
+ * stride below the length; n = 0 is FTS_API_OK; FTS_API_EINVAL for a NULL array, an unknown
+ * curve or n > 2^22.  isk, r and every draw are wiped from the call's host and device staging
+ * on every way out (isk32_out is the caller's).  Not hardened against timing side channels. */
+int fts_idemix_issuer_keygen_batch(int device, int curve_id, size_t n, uint64_t seed, uint8_t* isk32_out,
+                                   uint8_t* ipk_out, size_t ipk_stride, uint32_t* ipk_len);
+/* HIP-event durations (ms) of this process's last check call ([0]) and last keygen call ([1]),
+ * kernels only, summed over tiles. */
+int fts_idemix_issuer_key_last_timings(float* ms2);
+/* Host-only (tests): key i's draws at `seed` (not FTS_SEED_OS_RANDOM), 32 B big-endian each, in
+ * the order above: the nine that key generation consumes, then the stream's next value, which
+ * it does not (ten values). */
+int fts_debug_idemix_keygen_draws(int curve_id, uint64_t seed, uint64_t i, uint8_t* out10x32);
+/* Host-only (tests): the host's part of the check (host/ipk_write.hpp): *status as
+ * fts_idemix_ipk_check_batch would leave it before the device runs, hash32 as hash32_out. */
+int fts_debug_idemix_ipk_parse(int curve_id, const uint8_t* ipk, size_t ipk_len, int32_t* status, uint8_t* hash32);
 
 #ifdef __cplusplus
 }
